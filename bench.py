@@ -3,7 +3,18 @@
 dense fp64 tableau (BASELINE.json metric), 1/2/4/8 MI355X.
 
     python bench.py [--gpus N] [--steps S] [--warmup W] [--workload c3|c2]
-                    [--step-unit block|pivot]
+                    [--step-unit block|pivot] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the S steps and prints the result line
+(headline figure, ms_per_step, the roofline of the timed window's own passes).
+--full adds every other leg (see the last paragraph): the --step-unit pivot
+window, the eager rank-1 roofline window, the CPU baselines, the pivot log
+against the committed oracle digests, and with N > 1 the other exchange's
+window; without it those fields of the line are null.  --dump-outputs DIR
+writes what the timed window left, as a caller receives it, to DIR/<name>.npy
+(float64): the result's x, y, objective and pivot log, and a fixed seeded
+sample of tableau rows.  The LP is generated from the workload's seed, so two
+runs with the same arguments see identical inputs.
 
 What is timed: pivots of ONE LP whose tableau is resident in HBM, row-block
 partitioned over the N ranks (one process per GPU, exchange inside libdlp).  For
@@ -28,9 +39,9 @@ bytes per launch = 16 * rows_local * (N + 1) (one read + one write of every
 constraint element) over its mean launch time from HIP events
 on the session stream.  `traffic` is the committed rocprofv3 PMC summary of the
 same kernel at the same geometry (profiles/, tools/pmc_summary.py), or null
-when none matches.  cpu_baseline (rank 0, N = 1 only) is the in-repo CPU
-oracle (same pivot rule, test infrastructure) on a bounded sample of the same
-LP: all host threads available to this process, then 1 thread.
+when none matches.  With --full: cpu_baseline (rank 0, N = 1 only) is the
+in-repo CPU oracle (same pivot rule, test infrastructure) on a bounded sample
+of the same LP: all host threads available to this process, then 1 thread.
 """
 from __future__ import annotations
 
@@ -78,6 +89,13 @@ def parse():
                     help="block: a step is K pivots + one rank-K tableau pass; pivot: one pivot")
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS) + ["c5"],
                     help="c5: the batched small-LP workload (a step = one solve of the whole batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline window: the pivot-step window, the eager "
+                         "rank-1 roofline window, the CPU baselines, the pivot log against the oracle digests, "
+                         "N > 1: the other exchange's window; c5: the single-LP latency roofline and the CPU "
+                         "baseline (each can still be switched off by its own --no-... option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what they computed to DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=8.0,
                     help="CPU baseline: time budget of each oracle window (all CPUs, OMP share, 1)")
@@ -114,7 +132,12 @@ def parse():
                          "after one rank fails")
     ap.add_argument("--stub-worker", default=None, choices=("ok", "fail1", "hang1"),
                     help=argparse.SUPPRESS)   # tests/test_bench_launcher.py: a rank that does no GPU work
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:   # a plain run: the headline window only
+        args.no_cpu_baseline = args.no_eager_window = args.no_pivot_window = True
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
@@ -522,6 +545,40 @@ def alt_exchange_window(sess, dist, barrier_sync, args, L, torch):
     return out
 
 
+DUMP_ROWS = 32          # tableau rows in a dump: 33 rows x 65,537 doubles = 17 MB at C3
+DUMP_SEED = 0x5EED
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64 (the solver's own precision;
+    its integers, pivot indices and counts, are exact in it)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def session_outputs(sess, rank, world):
+    """What the timed window left, as its caller receives it: the result (x, y, objective, the
+    pivot log: replicated, so rank 0's) and DUMP_ROWS rows of this rank's tableau block (a fixed
+    seeded choice of local rows, each in full logical width) with the objective row below them."""
+    import numpy as np
+    out = {}
+    if rank == 0:
+        res = sess.result()
+        log = res.pivot_log
+        out.update({"x": res.x, "y": res.y, "objective": [res.objective], "num_pivots": [res.num_pivots],
+                    "pivot_log": np.stack([log[f].astype(np.float64) for f in
+                                           ("q", "p", "leaving", "ratio", "objective")], axis=1)})
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(sess.rows, size=min(DUMP_ROWS, sess.rows),
+                                                           replace=False))
+    sample = [sess.read_rows(int(r), 1)[0] for r in rows] + [sess.read_rows(sess.rows, 1)[0]]
+    tag = "" if world == 1 else f"_rank{rank}"
+    out["tableau_rows" + tag] = np.stack(sample)
+    out["tableau_row_index" + tag] = np.concatenate([rows + sess.row_first, [-1]])   # -1: the objective row
+    return out
+
+
 def c5_cpu_baseline(budget_s):
     """The oracle (same rule, 1 thread) on consecutive LPs of the C5 batch until budget_s of
     solve time (generation not timed): LPs/s on one core."""
@@ -616,14 +673,20 @@ def c5_main(args):
         pv = torch.tensor(piv, dtype=torch.int64, device="cuda")
         dist.all_reduce(pv, op=dist.ReduceOp.SUM)
         piv = [int(v) for v in pv.tolist()]
+    if args.dump_outputs:   # the last timed solve, as batched_solve returned it (this rank's LPs)
+        tag = "" if world == 1 else f"_rank{rank}"
+        write_outputs(args.dump_outputs, {"objective" + tag: br.objective, "status" + tag: br.status,
+                                          "num_pivots" + tag: br.num_pivots})
     occ = dlp.batched_occupancy(m, n, local)
     cus = torch.cuda.get_device_properties(local).multi_processor_count
-    # single-LP serial latency: 256 LPs of the batch, one per CU
-    one = dlp.batched_solve(min(256, nlp), m, n, seed, device=local, log_cap=0)
-    t1 = one.kernel_ms * 1e-3 / max(int(one.num_pivots.max()), 1)
     resident = min(nlp, occ["lps_per_cu"] * cus)
-    peak = resident / t1   # pivots/s with every resident LP at the single-LP latency
     achieved = piv[-1] * args.steps / kern     # pivots of the whole batch (all ranks) per second
+    t1 = peak = None
+    if args.full:
+        # single-LP serial latency: 256 LPs of the batch, one per CU
+        one = dlp.batched_solve(min(256, nlp), m, n, seed, device=local, log_cap=0)
+        t1 = one.kernel_ms * 1e-3 / max(int(one.num_pivots.max()), 1)
+        peak = resident / t1   # pivots/s with every resident LP at the single-LP latency
     pivots_lp = piv[-1] / C5["nlp"]
     if rank == 0:
         total = C5["nlp"] * args.steps
@@ -645,10 +708,10 @@ def c5_main(args):
             "wall_lps_per_s": total / wall,
             "occupancy": dict(occ, cus=cus, resident_lps=resident),
             "roofline": {"bound": "latency", "unit": "pivots/s", "achieved": achieved, "peak": peak,
-                         "frac": achieved / peak,
+                         "frac": achieved / peak if peak else None,
                          "model": ("peak = resident LPs (VGPR/LDS occupancy) / single-LP pivot latency; "
-                                   "single-LP latency from 256 LPs one per CU"),
-                         "single_lp_us_per_pivot": t1 * 1e6,
+                                   "single-LP latency from 256 LPs one per CU (a run of its own: --full)"),
+                         "single_lp_us_per_pivot": t1 * 1e6 if t1 else None,
                          "batch_us_per_pivot_per_lp": resident / achieved * 1e6,
                          "hbm_frac": bytes_solve / (kern / args.steps) / 1e9 / HBM_PEAK_GBS,
                          # hardware-anchored: the VALU-issue and LDS busy fractions of the
@@ -657,6 +720,7 @@ def c5_main(args):
                          "fp64_frac": (2.0 * piv[-1] * (m + 1) * (m + n + 1) / (kern / args.steps) / 1e12
                                        / FP64_PEAK_TFS)},
             "cpu_baseline": None if (world > 1 or args.no_cpu_baseline) else c5_cpu_baseline(args.cpu_seconds),
+            "full": args.full,
         }
         print(json.dumps(line), flush=True)
     if dist is not None:
@@ -774,6 +838,8 @@ def main():
     bytes_launch = 16.0 * (rows_local + (1 if K == 1 else 0)) * N1
     achieved = bytes_launch / (upd_ms * 1e-3) / 1e9 if upd_ms > 0 else None   # timing 0: untimed
     obj_after = None
+    if args.dump_outputs:   # the state the timed window left, before any further window moves it on
+        write_outputs(args.dump_outputs, session_outputs(sess, rank, world))
 
     # the same LP continues: a --step-unit pivot window of args.steps pivots beside the main
     # figure (its last pass covers a partial block), timed the same way
@@ -799,13 +865,13 @@ def main():
 
     res = sess.result()
     obj_after = res.objective
-    parity = log_parity(args.workload, res.pivot_log) if rank == 0 else None
+    parity = log_parity(args.workload, res.pivot_log) if (rank == 0 and args.full) else None
 
     # N > 1: the same LP continues for args.alt_pivots pivots through the OTHER exchange
     # (RCCL collectives <-> owner-rooted peer stores), timed the same way, so that one
     # scaling run measures both; a failure to switch or to run is reported, not fatal
     alt = None
-    if dist is not None and args.alt_pivots > 0 and K > 1 and run_fallback is None:
+    if args.full and dist is not None and args.alt_pivots > 0 and K > 1 and run_fallback is None:
         alt = alt_exchange_window(sess, dist, barrier_sync, args, L, torch)
         if alt.get("pivots_per_s") and rank == 0:
             alt["pivot_log_vs_oracle"] = log_parity(args.workload, sess.result().pivot_log)
@@ -928,6 +994,7 @@ def main():
             "pivot_log_vs_oracle": parity,
             "cpu_baseline": cpu,
             "geometry": geo,
+            "full": args.full,
         }
         print(json.dumps(line), flush=True)
     if dist is not None:

@@ -41,3 +41,41 @@ def test_committed_traffic_for_the_default_bench_geometry():
     with open(os.path.join(ROOT, ".gpurunignore")) as f:
         pats = [line.strip() for line in f if line.strip()]
     assert not any(p.strip("./").startswith("profiles") for p in pats)
+
+
+def _parse(monkeypatch, *argv):
+    monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+    return bench.parse()
+
+
+def test_plain_run_is_the_headline_window_only(monkeypatch):
+    """Without --full every leg beside the timed window is off; --full turns them on again and
+    each keeps its own switch."""
+    a = _parse(monkeypatch, "--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_cpu_baseline and a.no_eager_window and a.no_pivot_window
+    a = _parse(monkeypatch, "--full", "--no-eager-window", "--dump-outputs", "d")
+    assert a.full and a.dump_outputs == "d"
+    assert not a.no_cpu_baseline and not a.no_pivot_window and a.no_eager_window
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: one float64 .npy per array, integers exact; the tableau sample is the same
+    seeded choice of rows on every run, the objective row last."""
+    import numpy as np
+
+    class Sess:   # the two calls session_outputs makes on a rank that is not rank 0
+        rows, row_first, ld = 100, 300, 8
+
+        def read_rows(self, first, count):
+            return np.full((count, self.ld), float(first))
+
+    outs = [bench.session_outputs(Sess(), 1, 2) for _ in range(2)]
+    assert sorted(outs[0]) == ["tableau_row_index_rank1", "tableau_rows_rank1"]
+    idx, rows = outs[0]["tableau_row_index_rank1"], outs[0]["tableau_rows_rank1"]
+    assert (idx == outs[1]["tableau_row_index_rank1"]).all() and idx[-1] == -1
+    assert rows.shape == (bench.DUMP_ROWS + 1, 8) and len(set(idx)) == bench.DUMP_ROWS + 1
+    assert (rows[:-1, 0] == idx[:-1] - 300).all() and rows[-1, 0] == 100   # local rows, then the objective row
+    bench.write_outputs(str(tmp_path / "o"), {"a": np.arange(3, dtype=np.int64) + 2 ** 40, "b": [1.5]})
+    a, b = np.load(tmp_path / "o" / "a.npy"), np.load(tmp_path / "o" / "b.npy")
+    assert a.dtype == b.dtype == np.float64 and a.tolist() == [2 ** 40, 2 ** 40 + 1, 2 ** 40 + 2] and b.tolist() == [1.5]

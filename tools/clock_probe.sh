@@ -6,7 +6,7 @@
 set -o pipefail
 R=$(pwd); TAG=$1; shift
 OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
-timeout -k 10 200 python -u bench.py --no-cpu-baseline --no-eager-window --steps 60 "$@" > $OUT/clk_bench.json 2> $OUT/clk_bench.err &
+timeout -k 10 200 python -u bench.py --full --no-cpu-baseline --no-eager-window --steps 60 "$@" > $OUT/clk_bench.json 2> $OUT/clk_bench.err &
 B=$!
 for i in $(seq 1 24); do
   sleep 0.5

@@ -20,7 +20,7 @@ tail -3 $OUT/gpu_tests.txt
 timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1 \
     || { cat $OUT/smoke.txt; exit 1; }
 cat $OUT/smoke.txt
-timeout -k 10 300 python -u bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err \
+timeout -k 10 300 python -u bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err \
     || { cat $OUT/bench_default.err; exit 1; }
 cat $OUT/bench_default.json
 echo "check $TAG done"
