@@ -94,8 +94,24 @@ class MWIter(C.Structure):
                 ("weighted_budget", C.c_double)]
 
 
+class BatchDenseIn(C.Structure):
+    """dlp_batch_dense_in: the caller's LPs of dlp_batched_solve_dense."""
+    _fields_ = [("A", C.c_void_p), ("b", C.c_void_p), ("c", C.c_void_p),
+                ("strideA", C.c_int64), ("strideb", C.c_int64), ("stridec", C.c_int64),
+                ("device", C.c_int32), ("pad_", C.c_int32)]
+
+
+class BatchOut(C.Structure):
+    """dlp_batch_out: host output pointers of dlp_batched_solve_dense (NULL: skipped)."""
+    _fields_ = [("objective", C.POINTER(C.c_double)), ("status", C.POINTER(C.c_int32)),
+                ("npivots", C.POINTER(C.c_int64)), ("basis", C.POINTER(C.c_int32)),
+                ("logs", C.POINTER(Pivot)), ("log_cap", C.c_int64),
+                ("x", C.POINTER(C.c_double)), ("y", C.POINTER(C.c_double)),
+                ("kernel_ms", C.POINTER(C.c_double))]
+
+
 assert C.sizeof(Pivot) == 32 and C.sizeof(Candidate) == 32 and C.sizeof(MWIter) == 48
-assert C.sizeof(MWOptions) == 40
+assert C.sizeof(MWOptions) == 40 and C.sizeof(BatchDenseIn) == 56 and C.sizeof(BatchOut) == 72
 
 _P = C.c_void_p
 _I64 = C.c_int64
@@ -198,6 +214,8 @@ SIGNATURES = [
     ("dlp_batched_solve", C.c_int,
      [C.c_int, _I64, _I64, _I64, C.c_uint64, C.POINTER(Options), _DP, C.POINTER(_I32),
       C.POINTER(_I64), C.POINTER(_I32), C.POINTER(Pivot), _I64, _DP]),
+    ("dlp_batched_solve_dense", C.c_int,
+     [_I64, _I64, _I64, C.POINTER(BatchDenseIn), C.POINTER(Options), C.POINTER(BatchOut)]),
 ]
 
 _lib = None

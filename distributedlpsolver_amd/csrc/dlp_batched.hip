@@ -84,6 +84,24 @@ struct BatchOut {
     dlp_pivot* logs;
     int64_t log_cap;
     uint64_t* stamps;   // diagnostics (DLP_BATCH_STAMPS): LP 0's phase clocks, [64 pivots][8]
+    double* x;          // [nlp * n], [nlp * m]: the solution vectors (NULL: not written)
+    double* y;
+};
+
+// Where a batch kernel takes LP k's data from.  GenIn: the generated full-layout tableaus (LP k
+// at T + k * (m+1) * ld).  DenseIn: the caller's A_k (m x n row-major, no padding), b_k, c_k at
+// strides sA, sb, sc doubles (0: one array shared by every LP), read straight into the
+// condensed tableau: slot j of row i is A_k[i][j], the RHS b_k[i], the objective row -c_k[j]
+// with value +0 (the single-LP dense fill), and no full-layout copy passes through HBM.
+struct GenIn {
+    static constexpr bool dense = false;
+    const double* T;
+    int64_t ld;
+};
+struct DenseIn {
+    static constexpr bool dense = true;
+    const double *A, *b, *c;
+    int64_t sA, sb, sc;
 };
 
 // One workgroup = one LP.  The LDS holds only the NONBASIC columns of the
@@ -102,8 +120,8 @@ struct BatchOut {
 // a fma / division whose result does not).  Pricing runs over the slots with
 // the full tableau's order: min z, ties -> smallest VARIABLE index; Bland ->
 // the smallest variable index with z < -tol.
-__global__ __launch_bounds__(512) void batched_solve_kernel(const double* __restrict__ Tg,
-                                                            int64_t ldg, int m, int n,
+template <class In>
+__global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
                                                             int64_t max_pivots, int pricing,
                                                             double tol_dj, double tol_piv,
                                                             BatchOut out) {
@@ -114,15 +132,30 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(const double* __rest
     double* prow = colq + (m + 1);                      // W
     int32_t* var = (int32_t*)(prow + W);                // n
     int32_t* basis = var + n;                           // m
-    // scratch: [0] q (variable), [1] slot of q, [2] p, [3] status, [4] bland
+    // scratch: [0] q (variable), [1] slot of q, [2] p, [3] status, [4] bland, [5] dense: some b_i not >= 0
     int32_t* sI = basis + m;
     double* sD = (double*)(sI + 6 + ((n + m) & 1));     // piv, ratio (8-B aligned)
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int64_t lp = blockIdx.x;
-    const double* src = Tg + lp * (m + 1) * ldg;
-    for (int i = 0; i <= m; ++i)
-        for (int s = tid; s < W; s += blockDim.x) T[i * W + s] = src[(int64_t)i * ldg + (s < n ? s : N)];
+    if constexpr (!In::dense) {
+        const double* __restrict__ src = in.T + lp * (m + 1) * in.ld;
+        for (int i = 0; i <= m; ++i)
+            for (int s = tid; s < W; s += blockDim.x) T[i * W + s] = src[(int64_t)i * in.ld + (s < n ? s : N)];
+    } else {
+        const double* __restrict__ A = in.A + lp * in.sA;
+        const double* __restrict__ b = in.b + lp * in.sb;
+        const double* __restrict__ c = in.c + lp * in.sc;
+        for (int i = 0; i < m; ++i)
+            for (int s = tid; s < W; s += blockDim.x) T[i * W + s] = s < n ? A[(int64_t)i * n + s] : b[i];
+        for (int s = tid; s < W; s += blockDim.x) T[m * W + s] = s < n ? -c[s] : 0.0;
+        if (wid == 0) {   // an LP with a negative or NaN b_i is rejected, not solved
+            bool bad = false;
+            for (int i = lane; i < m; i += 64) bad |= !(b[i] >= 0.0);
+            const uint64_t anyb = __ballot(bad);
+            if (lane == 0) sI[5] = anyb != 0 ? 1 : 0;
+        }
+    }
     for (int s = tid; s < n; s += blockDim.x) var[s] = s;
     for (int i = tid; i < m; i += blockDim.x) basis[i] = n + i;
     if (tid == 0) {
@@ -130,6 +163,23 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(const double* __rest
         sI[4] = pricing == DLP_PRICING_BLAND ? 1 : 0;
     }
     __syncthreads();
+    if constexpr (In::dense) {
+        if (sI[5]) {   // (uniform) DLP_ERR_ARG, no pivots, the slack basis, NaN values
+            const double nan = __builtin_nan("");
+            if (tid == 0) {
+                if (out.status) out.status[lp] = DLP_ERR_ARG;
+                if (out.npivots) out.npivots[lp] = 0;
+                if (out.objective) out.objective[lp] = nan;
+            }
+            if (out.basis)
+                for (int i = tid; i < m; i += blockDim.x) out.basis[lp * m + i] = n + i;
+            if (out.x)
+                for (int j = tid; j < n; j += blockDim.x) out.x[lp * n + j] = nan;
+            if (out.y)
+                for (int i = tid; i < m; i += blockDim.x) out.y[lp * m + i] = nan;
+            return;
+        }
+    }
 
     int64_t k = 0;
     for (; k < max_pivots; ++k) {
@@ -272,6 +322,23 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(const double* __rest
     }
     if (out.basis)
         for (int i = tid; i < m; i += blockDim.x) out.basis[lp * m + i] = basis[i];
+    // x and y from the tableau as it stands, every index written exactly once (no zero fill):
+    // a nonbasic variable by its slot (x_j = 0, y_i = the slack's reduced cost), a basic one by
+    // its row (x_j = the row's RHS, y_i = +0)
+    if (out.x || out.y) {
+        double* x = out.x ? out.x + lp * n : nullptr;
+        double* y = out.y ? out.y + lp * m : nullptr;
+        for (int s = tid; s < n; s += blockDim.x) {
+            const int v = var[s];
+            if (v < n) { if (x) x[v] = 0.0; }
+            else if (y) y[v - n] = T[m * W + s];
+        }
+        for (int i = tid; i < m; i += blockDim.x) {
+            const int v = basis[i];
+            if (v < n) { if (x) x[v] = T[i * W + n]; }
+            else if (y) y[v - n] = 0.0;
+        }
+    }
 }
 
 // C5, register-resident (round 3): at m = 64 one LANE owns one slot (column) of the
@@ -459,8 +526,8 @@ __device__ __forceinline__ void move_if_row(double& dst, double src, int p) {
         : [s] "v"(src), [p] "s"(p), [row] "n"(ROW)
         : "scc");
 }
-template <int M, int NW>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) void batched_reg_kernel(const double* __restrict__ Tg, int64_t ldg, int n,
+template <int M, int NW, class In>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) void batched_reg_kernel(In in, int n,
                                                            int64_t max_pivots, int pricing, double tol_dj,
                                                            double tol_piv, BatchOut out) {
     static_assert(M == 64, "one ratio-test row per lane of wave 0");
@@ -472,6 +539,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
     __shared__ int32_t s_p, s_leave, s_bland;
     __shared__ double s_piv;
     __shared__ uint64_t s_zm;   // rows 0..63 of the entering column that are +-0 (the elimination's skip rule)
+    __shared__ int32_t s_bad;   // dense input: some b_i is not >= 0
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int N = n + M;
     const int sl = tid;              // this lane's slot: < n a variable's column
@@ -481,25 +549,61 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
     // buffer loads, one lane offset and the row in the scalar offset (a flat load per row
     // would hold 65 64-bit addresses in VGPRs next to the 65 values); lanes past the slots
     // read out of range, which returns +0
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(Tg + lp * (int64_t)R * ldg), (short)0, (int)((int64_t)R * ldg * 8), 0x00020000);
     const int voff = own ? sl * 8 : 0x7fffff00;
     double t[R];
-    each<R>([&](auto I) {
-        t[I] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, (int)(I * ldg * 8), 0));
-    });
     // wave 0, lane i keeps row i's RHS (the ratio test's) and every lane of wave 0 the objective
     // value T[M][N], each updated with the operations a column slot's elimination applies (same
     // bits): the RHS column needs no slot of its own, so n columns take ceil(n / 64) waves (round
     // 4: 64 x 128 in 2 waves instead of 3, 64 x 64 in 1 instead of 2; more LPs per CU)
     double rr = 0.0, zr = 0.0;
-    if (wid == 0) {
-        rr = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(((int64_t)lane * ldg + N) * 8), 0, 0));
-        zr = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(((int64_t)M * ldg + N) * 8), 0, 0));
+    if constexpr (!In::dense) {
+        const int64_t ldg = in.ld;
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)(in.T + lp * (int64_t)R * ldg), (short)0, (int)((int64_t)R * ldg * 8), 0x00020000);
+        each<R>([&](auto I) {
+            t[I] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, (int)(I * ldg * 8), 0));
+        });
+        if (wid == 0) {
+            rr = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(((int64_t)lane * ldg + N) * 8), 0, 0));
+            zr = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(((int64_t)M * ldg + N) * 8), 0, 0));
+        }
+    } else {
+        // the same loads from the caller's arrays: the resource on A_k (M x n doubles, row I at
+        // scalar offset I * n * 8), a second one on c_k for the objective row -c[slot]; wave 0,
+        // lane i takes b_k[i], the objective value starts at +0
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)(in.A + lp * in.sA), (short)0, M * n * 8, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)(in.c + lp * in.sc), (short)0, n * 8, 0x00020000);
+        each<M>([&](auto I) {
+            t[I] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, (int)I * n * 8, 0));
+        });
+        t[M] = -__builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rc, voff, 0, 0));
+        if (wid == 0) {
+            rr = in.b[lp * in.sb + lane];
+            // an LP with a negative or NaN b_i is rejected, not solved
+            const uint64_t anyb = __ballot(!(rr >= 0.0));
+            if (lane == 0) s_bad = anyb != 0 ? 1 : 0;
+        }
     }
     for (int i = tid; i < M; i += blockDim.x) s_basis[i] = n + i;
     if (tid == 0) s_bland = pricing == DLP_PRICING_BLAND ? 1 : 0;
     __syncthreads();
+    if constexpr (In::dense) {
+        if (s_bad) {   // (uniform) DLP_ERR_ARG, no pivots, the slack basis, NaN values
+            const double nan = __builtin_nan("");
+            if (tid == 0) {
+                if (out.status) out.status[lp] = DLP_ERR_ARG;
+                if (out.npivots) out.npivots[lp] = 0;
+                if (out.objective) out.objective[lp] = nan;
+            }
+            if (out.basis)
+                for (int i = tid; i < M; i += blockDim.x) out.basis[lp * M + i] = n + i;
+            if (out.x && own) out.x[lp * n + sl] = nan;
+            if (out.y && wid == 0) out.y[lp * M + lane] = nan;
+            return;
+        }
+    }
     int status = DLP_RUNNING;
     int64_t k = 0;
     auto stamp = [&](int ph) {
@@ -659,6 +763,22 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
     }
     if (out.basis)
         for (int i = tid; i < M; i += blockDim.x) out.basis[lp * M + i] = s_basis[i];
+    // x and y from the tableau as it stands, every index written exactly once (no zero fill):
+    // a nonbasic variable by its slot's lane (x_j = 0, y_i = the slack's reduced cost), a basic
+    // one by its row's lane of wave 0 (x_j = the row's RHS, y_i = +0)
+    if (out.x || out.y) {
+        double* x = out.x ? out.x + lp * n : nullptr;
+        double* y = out.y ? out.y + lp * M : nullptr;
+        if (own) {
+            if (var < n) { if (x) x[var] = 0.0; }
+            else if (y) y[var - n] = t[M];
+        }
+        if (wid == 0) {
+            const int bv = s_basis[lane];
+            if (bv < n) { if (x) x[bv] = rr; }
+            else if (y) y[bv - n] = 0.0;
+        }
+    }
 }
 
 }  // namespace
@@ -681,10 +801,14 @@ struct BatchCtx {
     void* dB = nullptr;   size_t capB = 0;
     void* dL = nullptr;   size_t capL = 0;
     void* hOut = nullptr; size_t capH = 0;   // pinned
+    // dlp_batched_solve_dense: host inputs staged as A | b | c, and the x / y outputs
+    void* dIn = nullptr;  size_t capIn = 0;
+    void* dX = nullptr;   size_t capX = 0;
+    void* dY = nullptr;   size_t capY = 0;
     void free_all() {
         if (device >= 0) (void)hipSetDevice(device);
         if (s) (void)hipStreamSynchronize(s);
-        for (void* p : {dT, dOut, dB, dL})
+        for (void* p : {dT, dOut, dB, dL, dIn, dX, dY})
             if (p) (void)hipFree(p);
         if (hOut) (void)hipHostFree(hOut);
         if (e0) (void)hipEventDestroy(e0);
@@ -726,7 +850,8 @@ size_t batched_release(int device) {
         if (device >= 0 && d != device) continue;
         std::lock_guard<std::mutex> lk(g_batch_mu[d]);
         if (g_batch[d].device >= 0) {
-            n += g_batch[d].capT + g_batch[d].capOut + g_batch[d].capB + g_batch[d].capL;
+            n += g_batch[d].capT + g_batch[d].capOut + g_batch[d].capB + g_batch[d].capL +
+                 g_batch[d].capIn + g_batch[d].capX + g_batch[d].capY;
             g_batch[d].free_all();
         }
     }
@@ -767,15 +892,16 @@ extern "C" int dlp_batched_occupancy(int64_t m, int64_t n, int device, int32_t* 
     hipError_t e;
     if (reg) {
         threads = 64 * nw;
-        e = nw == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dlp::batched_reg_kernel<64, 1>, threads, 0)
-          : nw == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dlp::batched_reg_kernel<64, 2>, threads, 0)
-                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dlp::batched_reg_kernel<64, 3>, threads, 0);
+        using dlp::GenIn;
+        e = nw == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dlp::batched_reg_kernel<64, 1, GenIn>, threads, 0)
+          : nw == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dlp::batched_reg_kernel<64, 2, GenIn>, threads, 0)
+                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dlp::batched_reg_kernel<64, 3, GenIn>, threads, 0);
     } else {
         threads = lds > 40 * 1024 ? 512 : 256;
-        e = hipFuncSetAttribute((const void*)dlp::batched_solve_kernel,
+        e = hipFuncSetAttribute((const void*)dlp::batched_solve_kernel<dlp::GenIn>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e == hipSuccess)
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dlp::batched_solve_kernel, threads, lds);
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dlp::batched_solve_kernel<dlp::GenIn>, threads, lds);
     }
     if (e != hipSuccess) {
         dlp::set_error(std::string("dlp_batched_occupancy: ") + hipGetErrorString(e));
@@ -787,17 +913,29 @@ extern "C" int dlp_batched_occupancy(int64_t m, int64_t n, int device, int32_t* 
     return DLP_OK;
 }
 
-extern "C" int dlp_batched_solve(int kind, int64_t nlp, int64_t m, int64_t n, uint64_t seed,
-                                 const dlp_options* opt, double* objective, int32_t* status,
-                                 int64_t* npivots, int32_t* basis, dlp_pivot* logs,
-                                 int64_t log_cap, double* kernel_ms) {
-    dlp_options o;
-    if (opt) o = *opt; else dlp_options_default(&o);
-    if (nlp <= 0 || m <= 0 || n <= 0 || (kind != DLP_GEN_DENSE && kind != DLP_GEN_DEGENERATE) ||
-        nlp > 65535 * 16 || log_cap < 0) {
-        dlp::set_error("dlp_batched_solve: bad arguments");
-        return DLP_ERR_ARG;
-    }
+namespace {
+// One batch of nlp LPs of m x n: generated on the device from (kind, seed + k), or the caller's
+// arrays (din); the host outputs (NULL: skipped).  The arguments are already validated.
+struct BatchJob {
+    const char* who;
+    int64_t nlp, m, n;
+    int kind;
+    uint64_t seed;
+    const dlp_batch_dense_in* din;   // NULL: generated
+    dlp_batch_out out;
+};
+
+int batched_run(const dlp_options& o, const BatchJob& job) {
+    const int64_t nlp = job.nlp, m = job.m, n = job.n;
+    const dlp_batch_dense_in* din = job.din;
+    double* const objective = job.out.objective;
+    int32_t* const status = job.out.status;
+    int64_t* const npivots = job.out.npivots;
+    int32_t* const basis = job.out.basis;
+    dlp_pivot* const logs = job.out.logs;
+    const int64_t log_cap = job.out.log_cap;
+    double* const kernel_ms = job.out.kernel_ms;
+    const std::string who = job.who;
     const int64_t N = n + m, ldg = (N + 1 + 15) / 16 * 16;
     const size_t lds = sizeof(double) * ((m + 1) * (n + 1) + (m + 1) + (n + 1)) + sizeof(int32_t) * (n + m + 8) +
                        sizeof(double) * 2 + 16;
@@ -808,11 +946,11 @@ extern "C" int dlp_batched_solve(int kind, int64_t nlp, int64_t m, int64_t n, ui
         return DLP_ERR_NODEVICE;
     }
     if (o.device < 0 || o.device >= ndev) {
-        dlp::set_error("dlp_batched_solve: no such device");
+        dlp::set_error(who + ": no such device");
         return DLP_ERR_ARG;
     }
     if (lds > 160 * 1024) {
-        dlp::set_error("dlp_batched_solve: tableau does not fit in 160 KiB of LDS");
+        dlp::set_error(who + ": tableau does not fit in 160 KiB of LDS");
         return DLP_ERR_UNSUPPORTED;
     }
     DeviceGuard guard;
@@ -830,31 +968,61 @@ extern "C" int dlp_batched_solve(int kind, int64_t nlp, int64_t m, int64_t n, ui
     int64_t* dNp = nullptr;
     int32_t* dSt = nullptr;
     const bool want_log = logs && log_cap > 0;
+    // host inputs are staged packed (A | b | c, a shared array once); device inputs are read in place
+    const bool stage = din && !din->device;
+    const size_t cntA = din ? (size_t)(din->strideA ? nlp : 1) * m * n : 0;
+    const size_t cntb = din ? (size_t)(din->strideb ? nlp : 1) * m : 0;
+    const size_t cntc = din ? (size_t)(din->stridec ? nlp : 1) * n : 0;
     HIP_BTRY(hipSetDevice(o.device));
     c->device = o.device;
     if (!c->s) HIP_BTRY(hipStreamCreateWithFlags(&c->s, hipStreamNonBlocking));
     if (!c->e0) HIP_BTRY(hipEventCreate(&c->e0));
     if (!c->e1) HIP_BTRY(hipEventCreate(&c->e1));
-    HIP_BTRY(ensure_buf(&c->dT, &c->capT, sizeof(double) * nlp * (m + 1) * ldg));
+    if (!din) HIP_BTRY(ensure_buf(&c->dT, &c->capT, sizeof(double) * nlp * (m + 1) * ldg));
+    if (stage) HIP_BTRY(ensure_buf(&c->dIn, &c->capIn, sizeof(double) * (cntA + cntb + cntc)));
     HIP_BTRY(ensure_buf(&c->dOut, &c->capOut, bOut));
     HIP_BTRY(ensure_buf(&c->hOut, &c->capH, bOut, true));
     if (basis) HIP_BTRY(ensure_buf(&c->dB, &c->capB, sizeof(int32_t) * nlp * m));
     if (want_log) HIP_BTRY(ensure_buf(&c->dL, &c->capL, sizeof(dlp_pivot) * nlp * log_cap));
+    if (job.out.x) HIP_BTRY(ensure_buf(&c->dX, &c->capX, sizeof(double) * nlp * n));
+    if (job.out.y) HIP_BTRY(ensure_buf(&c->dY, &c->capY, sizeof(double) * nlp * m));
     dObj = (double*)c->dOut;
     dNp = (int64_t*)(dObj + nlp);
     dSt = (int32_t*)(dNp + nlp);
     {
         hipStream_t s = c->s;
-        double* dT = (double*)c->dT;
-        dim3 gg((unsigned)((m + 1 + 3) / 4), (unsigned)nlp);
-        dlp::batched_generate_kernel<<<gg, 256, 0, s>>>(dT, ldg, m, n, kind, seed);
-        HIP_BTRY(hipGetLastError());
+        dlp::GenIn gin{(const double*)c->dT, ldg};
+        dlp::DenseIn dn{};
+        if (!din) {
+            dim3 gg((unsigned)((m + 1 + 3) / 4), (unsigned)nlp);
+            dlp::batched_generate_kernel<<<gg, 256, 0, s>>>((double*)c->dT, ldg, m, n, job.kind, job.seed);
+            HIP_BTRY(hipGetLastError());
+        } else if (stage) {
+            // `per` doubles per LP at `stride` (0: one shared array) -> packed at dst
+            auto put = [&](double* dst, const double* src, int64_t per, int64_t stride) {
+                if (stride == 0 || stride == per)
+                    return hipMemcpyAsync(dst, src, sizeof(double) * per * (stride ? nlp : 1),
+                                          hipMemcpyHostToDevice, s);
+                return hipMemcpy2DAsync(dst, sizeof(double) * per, src, sizeof(double) * stride,
+                                        sizeof(double) * per, (size_t)nlp, hipMemcpyHostToDevice, s);
+            };
+            double* dA = (double*)c->dIn;
+            HIP_BTRY(put(dA, din->A, m * n, din->strideA));
+            HIP_BTRY(put(dA + cntA, din->b, m, din->strideb));
+            HIP_BTRY(put(dA + cntA + cntb, din->c, n, din->stridec));
+            dn = dlp::DenseIn{dA, dA + cntA, dA + cntA + cntb, din->strideA ? m * n : 0,
+                              din->strideb ? m : 0, din->stridec ? n : 0};
+        } else {
+            dn = dlp::DenseIn{din->A, din->b, din->c, din->strideA, din->strideb, din->stridec};
+        }
         bo.objective = dObj;
         bo.status = dSt;
         bo.npivots = dNp;
         bo.basis = basis ? (int32_t*)c->dB : nullptr;
         bo.logs = want_log ? (dlp_pivot*)c->dL : nullptr;
         bo.log_cap = want_log ? log_cap : 0;
+        bo.x = job.out.x ? (double*)c->dX : nullptr;
+        bo.y = job.out.y ? (double*)c->dY : nullptr;
         static const char* stamp_file = std::getenv("DLP_BATCH_STAMPS");
         if (stamp_file) {
             HIP_BTRY(hipMalloc(&dStamps, sizeof(uint64_t) * 64 * 8));
@@ -866,30 +1034,38 @@ extern "C" int dlp_batched_solve(int kind, int64_t nlp, int64_t m, int64_t n, ui
         static const bool force_lds = std::getenv("DLP_BATCH_LDS") && std::atoi(std::getenv("DLP_BATCH_LDS")) == 1;
         const int nw = (int)((n + 63) / 64);
         const bool reg = !force_lds && m == 64 && nw >= 1 && nw <= 3;
-        if (!reg)
-            HIP_BTRY(hipFuncSetAttribute((const void*)dlp::batched_solve_kernel,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_BTRY(hipEventRecord(c->e0, s));
-        if (reg) {
-            if (nw == 1)
-                dlp::batched_reg_kernel<64, 1><<<(unsigned)nlp, 64, 0, s>>>(dT, ldg, (int)n, o.max_pivots, o.pricing,
-                                                                          o.tol_dj, o.tol_piv, bo);
-            else if (nw == 2)
-                dlp::batched_reg_kernel<64, 2><<<(unsigned)nlp, 128, 0, s>>>(dT, ldg, (int)n, o.max_pivots, o.pricing,
-                                                                           o.tol_dj, o.tol_piv, bo);
-            else
-                dlp::batched_reg_kernel<64, 3><<<(unsigned)nlp, 192, 0, s>>>(dT, ldg, (int)n, o.max_pivots, o.pricing,
-                                                                           o.tol_dj, o.tol_piv, bo);
-        } else {
-            // 512 lanes per LP when few LPs share a CU (LDS > 40 KB each), else 256
-            const unsigned threads = lds > 40 * 1024 ? 512 : 256;
-            dlp::batched_solve_kernel<<<(unsigned)nlp, threads, lds, s>>>(
-                dT, ldg, (int)m, (int)n, o.max_pivots, o.pricing, o.tol_dj, o.tol_piv, bo);
-        }
-        HIP_BTRY(hipGetLastError());
+        // the kernel of this input kind (its own instantiation, so its own dynamic-LDS attribute),
+        // timed alone between e0 and e1
+        auto launch = [&](auto in) -> hipError_t {
+            using In = decltype(in);
+            hipError_t e = hipSuccess;
+            if (!reg)
+                e = hipFuncSetAttribute((const void*)dlp::batched_solve_kernel<In>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e == hipSuccess) e = hipEventRecord(c->e0, s);
+            if (e != hipSuccess) return e;
+            if (reg) {
+                if (nw == 1)
+                    dlp::batched_reg_kernel<64, 1, In><<<(unsigned)nlp, 64, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
+                                                                                  o.tol_dj, o.tol_piv, bo);
+                else if (nw == 2)
+                    dlp::batched_reg_kernel<64, 2, In><<<(unsigned)nlp, 128, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
+                                                                                   o.tol_dj, o.tol_piv, bo);
+                else
+                    dlp::batched_reg_kernel<64, 3, In><<<(unsigned)nlp, 192, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
+                                                                                   o.tol_dj, o.tol_piv, bo);
+            } else {
+                // 512 lanes per LP when few LPs share a CU (LDS > 40 KB each), else 256
+                const unsigned threads = lds > 40 * 1024 ? 512 : 256;
+                dlp::batched_solve_kernel<In><<<(unsigned)nlp, threads, lds, s>>>(
+                    in, (int)m, (int)n, o.max_pivots, o.pricing, o.tol_dj, o.tol_piv, bo);
+            }
+            return hipGetLastError();
+        };
+        HIP_BTRY(din ? launch(dn) : launch(gin));
         HIP_BTRY(hipEventRecord(c->e1, s));
         // read back only what the caller asked for: the packed outputs it wants in one copy
-        // (objective | pivot counts | status are contiguous), basis and logs when requested
+        // (objective | pivot counts | status are contiguous), basis, logs, x and y when requested
         const bool wo = objective != nullptr, wn = npivots != nullptr, ws = status != nullptr;
         if (wo || wn || ws) {
             const size_t from = wo ? 0 : wn ? sizeof(double) * nlp : (sizeof(double) + sizeof(int64_t)) * nlp;
@@ -900,6 +1076,10 @@ extern "C" int dlp_batched_solve(int kind, int64_t nlp, int64_t m, int64_t n, ui
         if (basis) HIP_BTRY(hipMemcpyAsync(basis, c->dB, sizeof(int32_t) * nlp * m, hipMemcpyDeviceToHost, s));
         if (want_log)
             HIP_BTRY(hipMemcpyAsync(logs, c->dL, sizeof(dlp_pivot) * nlp * log_cap, hipMemcpyDeviceToHost, s));
+        if (job.out.x)
+            HIP_BTRY(hipMemcpyAsync(job.out.x, c->dX, sizeof(double) * nlp * n, hipMemcpyDeviceToHost, s));
+        if (job.out.y)
+            HIP_BTRY(hipMemcpyAsync(job.out.y, c->dY, sizeof(double) * nlp * m, hipMemcpyDeviceToHost, s));
         HIP_BTRY(hipStreamSynchronize(s));
         if (kernel_ms) {
             float ms = 0.f;
@@ -922,4 +1102,45 @@ done:
     if (dStamps) (void)hipFree(dStamps);
     if (rc != DLP_OK || c == &priv) c->free_all();   // a failed context is rebuilt next call
     return rc;
+}
+}  // namespace
+
+extern "C" int dlp_batched_solve(int kind, int64_t nlp, int64_t m, int64_t n, uint64_t seed,
+                                 const dlp_options* opt, double* objective, int32_t* status,
+                                 int64_t* npivots, int32_t* basis, dlp_pivot* logs,
+                                 int64_t log_cap, double* kernel_ms) {
+    dlp_options o;
+    if (opt) o = *opt; else dlp_options_default(&o);
+    if (nlp <= 0 || m <= 0 || n <= 0 || (kind != DLP_GEN_DENSE && kind != DLP_GEN_DEGENERATE) ||
+        nlp > 65535 * 16 || log_cap < 0) {
+        dlp::set_error("dlp_batched_solve: bad arguments");
+        return DLP_ERR_ARG;
+    }
+    BatchJob job{};
+    job.who = "dlp_batched_solve";
+    job.nlp = nlp; job.m = m; job.n = n;
+    job.kind = kind; job.seed = seed;
+    job.out.objective = objective; job.out.status = status; job.out.npivots = npivots;
+    job.out.basis = basis; job.out.logs = logs; job.out.log_cap = log_cap;
+    job.out.kernel_ms = kernel_ms;
+    return batched_run(o, job);
+}
+
+extern "C" int dlp_batched_solve_dense(int64_t nlp, int64_t m, int64_t n, const dlp_batch_dense_in* in,
+                                       const dlp_options* opt, const dlp_batch_out* out) {
+    dlp_options o;
+    if (opt) o = *opt; else dlp_options_default(&o);
+    const auto bad_stride = [](int64_t s, int64_t need) { return s != 0 && s < need; };
+    if (nlp <= 0 || m <= 0 || n <= 0 || nlp > 65535 * 16 || !in || !out || out->log_cap < 0 || !in->A ||
+        !in->b || !in->c || (in->device != 0 && in->device != 1) || bad_stride(in->strideA, m * n) ||
+        bad_stride(in->strideb, m) || bad_stride(in->stridec, n)) {
+        dlp::set_error("dlp_batched_solve_dense: bad arguments");
+        return DLP_ERR_ARG;
+    }
+    BatchJob job{};
+    job.who = "dlp_batched_solve_dense";
+    job.nlp = nlp; job.m = m; job.n = n;
+    job.din = in;
+    job.out = *out;
+    return batched_run(o, job);
 }

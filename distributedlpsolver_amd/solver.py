@@ -479,6 +479,8 @@ class BatchResult:
     basis: np.ndarray | None
     logs: np.ndarray | None
     kernel_ms: float
+    x: np.ndarray | None = None   # batched_solve_dense: (nlp, n) and (nlp, m)
+    y: np.ndarray | None = None
 
 
 def batched_solve(nlp: int, m: int, n: int, seed: int, degenerate: bool = False,
@@ -498,6 +500,65 @@ def batched_solve(nlp: int, m: int, n: int, seed: int, degenerate: bool = False,
         logs.ctypes.data_as(C.POINTER(L.Pivot)) if logs is not None else None, log_cap,
         C.byref(ms)), "dlp_batched_solve")
     return BatchResult(obj, st, npv, basis, logs, ms.value)
+
+
+def batched_solve_dense(A, b, c, *, want_x: bool = True, want_y: bool = True, want_basis: bool = False,
+                        log_cap: int = 0, **opts) -> BatchResult:
+    """dlp_batched_solve_dense: the caller's own LPs max c_k^T x s.t. A_k x <= b_k, x >= 0
+    (b_k >= 0), all m x n, one workgroup each.  A is (nlp, m, n) or (m, n), b (nlp, m) or (m,),
+    c (nlp, n) or (n,); an unbatched argument is shared by every LP.  numpy arrays are copied to
+    the device on every call; torch float64 tensors on device ``opts.get("device", 0)`` are read
+    in place (pass those when the data is already on the GPU: the copy costs more than the
+    solve).  An LP with a negative or NaN b_i gets status ERR_ARG and NaN objective, x and y;
+    the others are solved."""
+    args = (A, b, c)
+    on_dev = [hasattr(v, "data_ptr") for v in args]
+    if any(on_dev) and not all(on_dev):
+        raise ValueError("A, b and c must be all numpy arrays or all device tensors")
+    if all(on_dev):
+        import torch   # only for callers who pass tensors: the package itself never needs it
+        device = int(opts.get("device", 0))
+        for name, v in zip("Abc", args):
+            if v.dtype != torch.float64:
+                raise ValueError(f"{name} must be a float64 tensor, not {v.dtype}")
+            if v.device.type != "cuda" or v.device.index != device:
+                raise ValueError(f"{name} is on {v.device}, the solve runs on device {device}")
+        A, b, c = (v.contiguous() for v in args)
+        torch.cuda.current_stream(device).synchronize()   # the inputs are complete before the call
+        ptrs = [v.data_ptr() for v in (A, b, c)]
+    else:
+        A, b, c = (np.ascontiguousarray(v, dtype=np.float64) for v in args)
+        ptrs = [v.ctypes.data for v in (A, b, c)]
+    sA, sb, sc = tuple(A.shape), tuple(b.shape), tuple(c.shape)
+    if len(sA) not in (2, 3) or len(sb) not in (1, 2) or len(sc) not in (1, 2):
+        raise ValueError("A must be (nlp, m, n) or (m, n), b (nlp, m) or (m,), c (nlp, n) or (n,)")
+    m, n = sA[-2:]
+    if sb[-1] != m or sc[-1] != n or m < 1 or n < 1:
+        raise ValueError(f"shape mismatch: A {sA}, b {sb}, c {sc}")
+    lead = {s[0] for s, nd in ((sA, 3), (sb, 2), (sc, 2)) if len(s) == nd}
+    if len(lead) > 1 or 0 in lead:
+        raise ValueError(f"inconsistent batch dimensions: A {sA}, b {sb}, c {sc}")
+    nlp = lead.pop() if lead else 1
+    o = options(**opts)
+    din = L.BatchDenseIn(ptrs[0], ptrs[1], ptrs[2], m * n if len(sA) == 3 else 0,
+                         m if len(sb) == 2 else 0, n if len(sc) == 2 else 0, 1 if all(on_dev) else 0, 0)
+    obj = np.zeros(nlp)
+    st = np.zeros(nlp, np.int32)
+    npv = np.zeros(nlp, np.int64)
+    basis = np.zeros((nlp, m), np.int32) if want_basis else None
+    logs = np.zeros((nlp, log_cap), PIVOT_DTYPE) if log_cap > 0 else None
+    x = np.zeros((nlp, n)) if want_x else None
+    y = np.zeros((nlp, m)) if want_y else None
+    ms = C.c_double()
+    out = L.BatchOut(_dptr(obj), st.ctypes.data_as(C.POINTER(C.c_int32)),
+                     npv.ctypes.data_as(C.POINTER(C.c_int64)),
+                     basis.ctypes.data_as(C.POINTER(C.c_int32)) if basis is not None else None,
+                     logs.ctypes.data_as(C.POINTER(L.Pivot)) if logs is not None else None, log_cap,
+                     _dptr(x) if x is not None else None, _dptr(y) if y is not None else None,
+                     C.pointer(ms))
+    L.check(L.lib().dlp_batched_solve_dense(nlp, m, n, C.byref(din), C.byref(o), C.byref(out)),
+            "dlp_batched_solve_dense")
+    return BatchResult(obj, st, npv, basis, logs, ms.value, x, y)
 
 
 def batched_occupancy(m: int, n: int, device: int = 0) -> dict:

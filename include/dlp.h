@@ -450,6 +450,57 @@ int dlp_batched_solve(int kind, int64_t nlp, int64_t m, int64_t n, uint64_t seed
                       const dlp_options* opt, double* objective, int32_t* status,
                       int64_t* npivots, int32_t* basis, dlp_pivot* logs, int64_t log_cap,
                       double* kernel_ms);
+/* The same batch solve on the caller's own LPs: nlp independent problems
+ *   max c_k^T x  s.t.  A_k x <= b_k, x >= 0, b_k >= 0,
+ * all of one shape m x n (the per-impression subproblems themselves, not a
+ * generated stand-in).  Pivot rule, tolerances and options are those of
+ * dlp_batched_solve; every LP's pivot sequence is bit-identical to a
+ * single-LP solve (dlp_problem_create_dense + dlp_solve).  The kernels read
+ * A, b and c directly; no full-layout tableau is built in device memory.
+ *
+ * Inputs: A_k is m x n row-major without padding, LP k's arrays start
+ * strideA / strideb / stridec doubles after LP k-1's.  A stride of 0 shares
+ * one array between all LPs; any other stride must be at least m*n, m, n
+ * (else DLP_ERR_ARG).  device = 0: host pointers (copied to the device on
+ * every call: at 4096 x (64 x 128) that copy is 268 MB and costs far more
+ * than the solve); device = 1: device pointers on opt->device whose contents
+ * are complete when the call is made (the solve runs on the library's own
+ * stream).
+ *
+ * Outputs: host pointers, NULL to skip.  objective, status, npivots, basis,
+ * logs + log_cap and kernel_ms (the solve kernel's device time alone) as in
+ * dlp_batched_solve; x[nlp*n] and y[nlp*m] with dlp_result_x / dlp_result_y's
+ * meaning (x_j: the RHS of the row whose basic variable is j, else 0; y_i:
+ * the reduced cost of slack n+i, 0 when it is basic), taken from the tableau
+ * as it stands for every status, DLP_UNBOUNDED and DLP_PIVOT_LIMIT included.
+ *
+ * An LP with some b_i that is not >= 0 (negative or NaN) is not solved:
+ * status[k] = DLP_ERR_ARG, npivots[k] = 0, objective[k] and its x and y NaN,
+ * its basis the slack basis; the other LPs are solved and the call returns
+ * DLP_OK.  Call-level errors, in this order: DLP_ERR_ARG (sizes, strides,
+ * NULL inputs, nlp > 65535*16), DLP_ERR_NODEVICE, DLP_ERR_UNSUPPORTED (the
+ * tableau does not fit 160 KiB of LDS). */
+typedef struct dlp_batch_dense_in {
+    const double* A;       /* nlp (or 1) x m x n */
+    const double* b;       /* nlp (or 1) x m */
+    const double* c;       /* nlp (or 1) x n */
+    int64_t strideA, strideb, stridec;   /* doubles between consecutive LPs; 0 = shared */
+    int32_t device;        /* 0 host pointers, 1 device pointers on opt->device */
+    int32_t pad_;
+} dlp_batch_dense_in;
+typedef struct dlp_batch_out {
+    double*    objective;  /* [nlp] */
+    int32_t*   status;     /* [nlp] */
+    int64_t*   npivots;    /* [nlp] */
+    int32_t*   basis;      /* [nlp*m] */
+    dlp_pivot* logs;       /* [nlp*log_cap] */
+    int64_t    log_cap;
+    double*    x;          /* [nlp*n] */
+    double*    y;          /* [nlp*m] */
+    double*    kernel_ms;  /* [1] */
+} dlp_batch_out;
+int dlp_batched_solve_dense(int64_t nlp, int64_t m, int64_t n, const dlp_batch_dense_in* in,
+                            const dlp_options* opt, const dlp_batch_out* out);
 /* The batch kernel dlp_batched_solve runs for m x n LPs on `device`: lanes per LP, LPs one CU
  * holds at once (VGPR / LDS occupancy) and whether it is the register-resident kernel (m = 64,
  * n <= 192) or the LDS one.  C5 is bound by per-pivot serial latency x this residency. */
