@@ -344,6 +344,15 @@ hipError_t launch_generate(const Geometry& g, int kind, int64_t m, int64_t n, ui
 hipError_t launch_gather_column(const double* T, int64_t ld, int64_t nrows, int64_t col,
                                 double* out, hipStream_t s);
 
+// dlp_reopt.hip: the objective row of g.T rebuilt for a new c (n doubles, device) from the
+// ascending list of the R rows whose basic variable costs cB != 0 (rlist / cblist, device); the
+// fold of DESIGN.md §18 (one ascending unfused fold per stored column).  basic (full layout only,
+// else NULL): [g.width] nonzero at the columns of basic variables (their z is +0.0).  Also sets
+// the state running again with the Bland state of the options (as launch_carry_in).
+hipError_t launch_reopt(const Geometry& g, int64_t n, int64_t N, const int32_t* rlist,
+                        const double* cblist, int64_t R, const double* c, const int32_t* basic,
+                        DevState* st, int pricing, hipStream_t s);
+
 // dlp_batched.hip: free the cached dlp_batched_solve contexts of `device` (-1: all); bytes freed
 size_t batched_release(int device);
 

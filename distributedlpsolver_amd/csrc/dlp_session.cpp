@@ -179,6 +179,14 @@ struct dlp_session {
     // them, from the device of every rank the peer connect saw (install_peers); 1 / 0 otherwise
     int coloc_n = 1, coloc_i = 0;
     int64_t ld_full = 0;   // condensed tableau: the row stride the full layout would have (read-outs)
+    bool step_open = false;   // caller-driven step: step_candidate done, step_update not yet
+    // dlp_session_set_objective, allocated at its first call: the contributing
+    // rows and their costs, c, the basic-column flags of the full layout; the kernel's events
+    int32_t* ro_rows = nullptr;
+    double* ro_cb = nullptr;
+    double* ro_c = nullptr;
+    int32_t* ro_basic = nullptr;
+    hipEvent_t ro_ev[2] = {nullptr, nullptr};
 };
 
 extern "C" int flush_pending(dlp_session* s);   // defined with the C entry points
@@ -533,8 +541,10 @@ void free_session(dlp_session* s) {
     void* dev[] = {s->Tb[0] ? s->Tb[0] : s->T, s->Tb[1], s->colq, s->prow_send, s->partials,
                    s->cand_send, s->cand_recv, s->pp, s->basis, s->st, s->log, s->d.C, s->d.Cc,
                    s->d.P, s->d.rhs, s->d.nzc, s->cl_gran, s->band_cnt, s->g.cd.slot_of, s->g.cd.var_of,
-                   s->g.cd.rst};
+                   s->g.cd.rst, s->ro_rows, s->ro_cb, s->ro_c, s->ro_basic};
     for (void* p : dev) pool_release(s, s->device, p);
+    for (hipEvent_t e : s->ro_ev)
+        if (e) (void)hipEventDestroy(e);
     if (s->la || s->dslot[1].C) {   // slot 0 aliases s->d
         void* sl[] = {s->dslot[1].C, s->dslot[1].Cc, s->dslot[1].P, s->dslot[1].nzc};
         for (void* p : sl) pool_release(s, s->device, p);
@@ -2812,6 +2822,7 @@ int dlp_session_step_candidate(dlp_session* s) {
     HIP_TRY(hipSetDevice(s->device));
     CALL_TRY(la_disable(s));   // the step API drives single-buffer blocks
     s->step_void = false;
+    s->step_open = true;
     // the Phase I -> II switch (drive-out pivots, carried row) runs on the eager
     // kernels in every session, as in dlp_session_run: apply a pending deferred
     // block first, since a forced pivot reads its row from the tableau
@@ -2847,6 +2858,7 @@ int dlp_session_step_select(dlp_session* s) {
 int dlp_session_step_update(dlp_session* s) {
     if (!s) return DLP_ERR_ARG;
     HIP_TRY(hipSetDevice(s->device));
+    s->step_open = false;
     if (s->step_void) return DLP_OK;
     if (s->step_kind == dlp_session::STEP_CARRY) {
         CALL_TRY(enqueue_carry_in(s));
@@ -2855,6 +2867,97 @@ int dlp_session_step_update(dlp_session* s) {
     if (s->d.K > 1 && s->step_kind == dlp_session::STEP_PIVOT) return step_update_defer(s);
     CALL_TRY(enqueue_update(s));
     s->launched += 1;
+    return DLP_OK;
+}
+
+// Warm re-optimisation: the resident tableau is a basic feasible tableau for any
+// objective, so a new c needs only a new objective row, z_j = c_B^T T[:, j] - c_j in the fixed
+// fold of dlp_reopt.hip; the session then prices again from its current basis.  Everything is
+// validated before anything is enqueued, so an error leaves the session as it was.
+int dlp_session_set_objective(dlp_session* s, const double* c, int64_t n, double* kernel_ms) {
+    if (!s || !c) return DLP_ERR_ARG;
+    if (s->general) {
+        set_error("dlp_session_set_objective: general / MPS problems are not supported (the objective "
+                  "lives in the standard form's columns and its Phase I row)");
+        return DLP_ERR_UNSUPPORTED;
+    }
+    if (s->nranks > 1 || s->exchange) {
+        set_error("dlp_session_set_objective: single-GPU sessions only (the fold over the rows would "
+                  "cross the ranks of a row-block session)");
+        return DLP_ERR_UNSUPPORTED;
+    }
+    if (n != s->n) {
+        set_error("dlp_session_set_objective: c has " + std::to_string(n) + " entries, the problem " +
+                  std::to_string(s->n) + " variables");
+        return DLP_ERR_ARG;
+    }
+    for (int64_t j = 0; j < n; ++j)
+        if (!std::isfinite(c[j])) {
+            set_error("dlp_session_set_objective: c[" + std::to_string(j) + "] is not finite");
+            return DLP_ERR_ARG;
+        }
+    if (s->status < 0) {
+        set_error("dlp_session_set_objective: the session has failed");
+        return DLP_ERR_STATE;
+    }
+    if (s->step_open) {
+        set_error("dlp_session_set_objective: a caller-driven step is in progress (finish it with "
+                  "dlp_session_step_update)");
+        return DLP_ERR_STATE;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->ro_rows) {
+        HIP_TRY(pool_alloc(s, s->device, (void**)&s->ro_rows, sizeof(int32_t) * std::max<int64_t>(s->m, 1)));
+        HIP_TRY(pool_alloc(s, s->device, (void**)&s->ro_cb, sizeof(double) * std::max<int64_t>(s->m, 1)));
+        HIP_TRY(pool_alloc(s, s->device, (void**)&s->ro_c, sizeof(double) * std::max<int64_t>(s->n, 1)));
+        if (!s->g.cd.on) HIP_TRY(pool_alloc(s, s->device, (void**)&s->ro_basic, sizeof(int32_t) * s->width));
+        HIP_TRY(hipEventCreate(&s->ro_ev[0]));
+        HIP_TRY(hipEventCreate(&s->ro_ev[1]));
+    }
+    // a deferred block in progress applied, a lookahead pass drained: T and the objective row
+    // both in s->T, every column of it current
+    CALL_TRY(flush_pending(s));
+    std::vector<int32_t> basis(s->m);
+    HIP_TRY(hipMemcpyAsync(basis.data(), s->basis, sizeof(int32_t) * s->m, hipMemcpyDeviceToHost, s->stream));
+    CALL_TRY(poll(s));   // (synchronises the stream; npivots and status as the device has them)
+    // the contributing rows, ascending: basic structural variables with a nonzero cost (a cost of
+    // -0.0 is zero: skipped)
+    std::vector<int32_t> rl;
+    std::vector<double> cb;
+    std::vector<int32_t> basic(s->g.cd.on ? 0 : s->width, 0);
+    for (int64_t i = 0; i < s->m; ++i) {
+        const int32_t v = basis[i];
+        if (!basic.empty() && v >= 0 && v < s->width) basic[v] = 1;
+        if (v >= 0 && v < s->n && c[v] != 0.0) {
+            rl.push_back((int32_t)i);
+            cb.push_back(c[v]);
+        }
+    }
+    const int64_t R = (int64_t)rl.size();
+    if (R > 0) {
+        HIP_TRY(hipMemcpyAsync(s->ro_rows, rl.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->ro_cb, cb.data(), sizeof(double) * R, hipMemcpyHostToDevice, s->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(s->ro_c, c, sizeof(double) * n, hipMemcpyHostToDevice, s->stream));
+    if (!basic.empty())
+        HIP_TRY(hipMemcpyAsync(s->ro_basic, basic.data(), sizeof(int32_t) * s->width, hipMemcpyHostToDevice,
+                               s->stream));
+    HIP_TRY(hipEventRecord(s->ro_ev[0], s->stream));
+    HIP_TRY(dlp::launch_reopt(s->g, s->n, s->N, s->ro_rows, s->ro_cb, R, s->ro_c, s->ro_basic, s->st,
+                              s->opt.pricing, s->stream));
+    HIP_TRY(hipEventRecord(s->ro_ev[1], s->stream));
+    // the pricing partials of the new row (the deferred kernels share the 512-column tiling)
+    HIP_TRY(dlp::launch_price_init(s->g, s->pp, s->opt.tol_dj, s->opt.update_variant, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (kernel_ms) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, s->ro_ev[0], s->ro_ev[1]));
+        *kernel_ms = ms;
+    }
+    s->status = DLP_RUNNING;
+    s->host_st->status = DLP_RUNNING;
+    // the pivot budget counts pivots: launches enqueued after the previous optimum did none
+    s->launched = s->npivots;
     return DLP_OK;
 }
 

@@ -275,6 +275,21 @@ class Session:
                                                      p.nbytes), "dlp_session_write_buffer")
         L.check(L.lib().dlp_session_step_update(self._h), "dlp_session_step_update")
 
+    def set_objective(self, c) -> float:
+        """Replace the objective by max c^T x and make the session runnable again from its
+        current basis (dlp_session_set_objective: a warm re-solve).  c: n float64 values.
+        Returns the device time (ms) of the objective-row rebuild."""
+        c = np.asarray(c)
+        if c.dtype.kind not in "fiu":
+            raise ValueError(f"c must be real-valued (float64), not {c.dtype}")
+        if c.shape != (self.problem.n,):
+            raise ValueError(f"c must have shape ({self.problem.n},), not {c.shape}")
+        c = np.ascontiguousarray(c, dtype=np.float64)
+        ms = C.c_double()
+        L.check(L.lib().dlp_session_set_objective(self._h, _dptr(c), c.shape[0], C.byref(ms)),
+                "dlp_session_set_objective")
+        return ms.value
+
     def status(self) -> tuple[int, int]:
         st, n = C.c_int(), C.c_int64()
         L.check(L.lib().dlp_session_status(self._h, C.byref(st), C.byref(n)), "dlp_session_status")

@@ -18,6 +18,9 @@
  *     R/instance.h:52-53, R/instance.cpp:117-134       the epsilon-approximate MW loop)
  *   GlobalProblem::ConstructPrimal per-iteration core  dlp_session_step_* (one pivot)
  *     R/global_problem.cpp:257-323                     dlp_session_run   (K pivots)
+ *   AllocationMW::RunAllocationMW: the same            dlp_session_set_objective + dlp_session_run
+ *     constraints re-weighted and solved again on      (warm re-solve from the resident basis
+ *     every iteration  R/allocation_mw.cpp:271-326     instead of a cold one)
  *   Instance::solution_ (private, no getter)           dlp_result_x / dlp_result_y
  *     R/instance.h:34
  *   "Dual Value" stdout  R/global_problem.cpp:320-322  dlp_result_objective
@@ -304,6 +307,38 @@ int dlp_session_run(dlp_session* s, int64_t max_pivots, int64_t* pivots_done);
 int dlp_session_step_candidate(dlp_session* s);
 int dlp_session_step_select(dlp_session* s);
 int dlp_session_step_update(dlp_session* s);
+/* Replace the objective of a live session by max c^T x (n doubles, host pointer) and make the
+ * session runnable again from its current basis (a warm re-solve: the resident tableau is a
+ * basic feasible tableau for every objective).  *kernel_ms (may be NULL): device time of the
+ * objective-row rebuild.
+ *
+ * Sessions: single-GPU sessions of dense, random and ad-allocation problems, on every storage
+ * path (eager, deferred full or condensed, lookahead, the one-launch small-LP path), at any time
+ * between runs and whatever the status (running, optimal, unbounded, stopped by a run budget).
+ *
+ * The rule (part of the parity definition).  basis[i] is the basic variable of
+ * row i; cB_i = c[basis[i]] if basis[i] < n, else +0.0 (slacks cost nothing).  For every stored
+ * column j, the RHS column included:
+ *   1. acc = -c_j for a structural variable j < n; acc = +0.0 for a slack and for the RHS (the
+ *      cold build's start values);
+ *   2. for rows i = 0, 1, ..., m-1 ascending, rows with cB_i == 0.0 skipped:
+ *      acc = acc + (cB_i * T[i][j]), the product rounded, then the sum rounded (no fma);
+ *   3. z_j = acc, except z_j = +0.0 for every basic variable j.
+ * One ascending fold per column: no atomics, no tree over rows, no row bands; the result does
+ * not depend on grid shape, tuning or layout.  Constraint rows, RHS, basis, pivot log and the
+ * pivot count are untouched.  Afterwards the status is DLP_RUNNING, the Bland state is reset as
+ * at the Phase II switch (Dantzig for DLP_PRICING_DANTZIG_BLAND, Bland for DLP_PRICING_BLAND),
+ * the pricing partials are rebuilt, options.max_pivots keeps counting pivots over the session's
+ * life and the pivot log is appended to.
+ *
+ * Errors, each leaving the session exactly as it was (everything is validated before anything
+ * is enqueued): DLP_ERR_ARG: s or c NULL, n differs from the problem's n, a c_j that is not
+ * finite; DLP_ERR_UNSUPPORTED (text in dlp_last_error): a general or MPS problem, a session
+ * created with nranks > 1 or an RCCL id; DLP_ERR_STATE: a failed session, or a caller-driven step
+ * in progress (step_candidate done, step_update not yet).
+ * Not covered: changes of b or A (they need a dual simplex), a device-pointer c, multi-rank
+ * sessions, general LPs, the batched API. */
+int dlp_session_set_objective(dlp_session* s, const double* c, int64_t n, double* kernel_ms);
 int dlp_session_buffer(dlp_session* s, int which, void** dev_ptr, size_t* bytes);
 /* Synchronous host copies of an exchange buffer (for host-side communicators). */
 int dlp_session_read_buffer(dlp_session* s, int which, void* host, size_t bytes);
