@@ -718,8 +718,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
         // the elimination's inputs, requested with p's (their LDS latency overlaps the pivot-row
         // division): the skip rule's row masks from the entering column's zero mask (SALU, no VALU
         // compare per row) and the entries for the DPP broadcast, 4 LDS reads per lane (elim8dpp)
-        const uint64_t zm = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(s_zm >> 32)) << 32) |
-                            __builtin_amdgcn_readfirstlane((uint32_t)s_zm);
+        // (readfirstlane returns int: both halves through uint32_t, or a set bit 31 — row 31's
+        // entry +-0 — sign-extends over rows 32..63 and their eliminations are skipped)
+        const uint64_t zm = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(s_zm >> 32)) << 32) |
+                            (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)s_zm);
         double cq[M / 16];
         each<M / 16>([&](auto G) { cq[G] = s_colq[16 * G + (lane & 15)]; });
         // (with them: the pivot, the objective row's entry and wave 0's row entry for its RHS update)

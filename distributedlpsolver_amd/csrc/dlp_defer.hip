@@ -1465,7 +1465,9 @@ __device__ __forceinline__ void pass_s_body(const double* __restrict__ T, double
         int last = -1;
         for (int l = 0; l < kb; ++l)
             if (bd->pl[l] == (int32_t)(i0 + r)) last = l;
-        cls[r] = last >= 0 ? last : (nz == kb ? kDense : (nz == 0 ? kUntouched : kSparse));
+        // (an empty block out of place is a copy: C and nzc are the previous block's, and
+        // fma(-c, +0, t) would turn a t = -0 into +0 where c < 0 or c = -0)
+        cls[r] = last >= 0 ? last : (kb == 0 || nz == 0 ? kUntouched : (nz == kb ? kDense : kSparse));
     }
     __syncthreads();
     // dense groups: U rows, every step of the block touches every row.  The next dense
@@ -1954,7 +1956,8 @@ __device__ inline void classify_band(int32_t* cls, const BlockDesc* __restrict__
                                      const int32_t* __restrict__ nzc, int64_t i0, int nr, int kb) {
     for (int r = threadIdx.x; r < nr; r += blockDim.x) {
         const int nz = nzc[i0 + r];
-        cls[r] = nz == kb ? kDense : (nz == 0 ? kUntouched : kSparse);
+        // (an empty block, out of place, is a copy: C and nzc are the previous block's)
+        cls[r] = kb == 0 || nz == 0 ? kUntouched : (nz == kb ? kDense : kSparse);
     }
     __syncthreads();
     for (int l = threadIdx.x; l < kb; l += blockDim.x) {
@@ -2517,6 +2520,24 @@ __global__ __launch_bounds__(256) void reset_cols_kernel(double* __restrict__ T,
     const int kb = *blkp;
     double* r = T + i * ld;
     for (int l = 0; l < kb; ++l) r[qs[l]] = (pl[l] == (int32_t)i) ? 1.0 : 0.0;
+}
+
+// A step that found no eligible row (DLP_UNBOUNDED) is no step of its block, but its ratio
+// kernel has written the entering column as the coefficients of step kb (C, counted in nzc),
+// where the passes expect the zeroed tail: fma(-a, P[kb] = +0, t) turns t = -0 into +0 where
+// a < 0 or a = -0.  Before the block's pass, that column goes back to +0 and out of the counts
+// (one lane per local row and the objective row; nothing to do in any other state).
+__global__ __launch_bounds__(256) void drop_failed_step_kernel(const DevState* __restrict__ st,
+                                                               const int32_t* __restrict__ blkp,
+                                                               double* __restrict__ C, int64_t ldc,
+                                                               int32_t* __restrict__ nzc, int64_t rows) {
+    if (st->status != DLP_UNBOUNDED) return;
+    const int kb = *blkp;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > rows || kb < 0 || kb >= ldc) return;
+    const double a = C[i * ldc + kb];
+    if (i < rows && a != 0.0) nzc[i] = nzc[i] - 1;
+    C[i * ldc + kb] = 0.0;
 }
 
 // Lookahead: the block just selected becomes st->seal[slot] (read by its pass and
@@ -3091,6 +3112,12 @@ hipError_t launch_flush_defer(const Geometry& g, const Defer& d, DevState* st, b
     uint32_t* bcnt = nullptr;
     if (bp && bp->cnt && seal >= 0 && Tout && Tout != g.T && band_pub_ok(*bp, g, d, rows_per_block))
         bcnt = bp->cnt + seal * bp->stride;
+    if (g.rows > 0 && d.C && d.nzc) {
+        drop_failed_step_kernel<<<(unsigned)((g.rows + 256) / 256), 256, 0, s>>>(
+            st, seal >= 0 ? &st->seal[seal].blk : &st->blk, d.C, d.ldc, d.nzc, g.rows);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
     if (g.cd.on) {
         const hipError_t e = launch_reset_cols(g, st, seal, s);
         if (e != hipSuccess) return e;

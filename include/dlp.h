@@ -176,7 +176,10 @@ typedef struct dlp_options {
     int32_t condensed;       /* deferred sessions (defer > 1) of dense / random / ad-allocation LPs:
                                 store only the n nonbasic columns + the RHS, the m basic columns
                                 being exact unit vectors (results, pivots and
-                                read-outs bit-identical to the full tableau): 1 = on where
+                                read-outs bit-identical to the full tableau, the read-outs up
+                                to the sign of a zero in a basic variable's column: there the
+                                full tableau keeps a caller's -0 that the rule left untouched,
+                                the condensed read-out gives the unit vector's +0): 1 = on where
                                 supported, -1 = off, 0 = auto (default: on; DLP_CONDENSED=0/1
                                 overrides auto) */
 } dlp_options;
