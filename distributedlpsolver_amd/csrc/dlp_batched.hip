@@ -10,6 +10,8 @@
 // IEEE division for the pivot row, fma elimination, colq == 0 rows untouched.
 // Reference analog: the per-impression subproblems solved independently in
 // GlobalProblem::ConstructPrimal, R/global_problem.cpp:270-274.
+// A dlp_batch keeps every LP's final state in HBM between calls and continues from it after new
+// objectives (the resident source and the keep switch below).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <new>
 #include <string>
 #include <utility>
 #include <vector>
@@ -94,15 +97,55 @@ struct BatchOut {
 // condensed tableau: slot j of row i is A_k[i][j], the RHS b_k[i], the objective row -c_k[j]
 // with value +0 (the single-LP dense fill), and no full-layout copy passes through HBM.
 struct GenIn {
-    static constexpr bool dense = false;
+    static constexpr bool dense = false, resident = false, keep = false;
     const double* T;
     int64_t ld;
 };
 struct DenseIn {
-    static constexpr bool dense = true;
+    static constexpr bool dense = true, resident = false, keep = false;
     const double *A, *b, *c;
     int64_t sA, sb, sc;
 };
+// The resident state of a dlp_batch, LP k's record at S + k * state_doubles(m, n):
+// the condensed tableau, row i's n slots then its RHS (row stride W = n + 1, the objective row
+// last, its RHS entry the objective value), then as int32 var[n] | basis[m] | the Bland flag |
+// the status.  Consecutive slots are consecutive doubles: the LDS kernel's slot loops and the
+// register kernel's buffer accesses (lane = slot in the vector offset, row in the scalar
+// offset) are both coalesced.  (One base pointer: the register kernel carries it through its
+// pivot loop in two SGPRs; two pointers were two SGPRs too many and spilled.)
+struct BatchState {
+    double* S;
+};
+__host__ __device__ inline int64_t state_doubles(int64_t m, int64_t n) {
+    return (m + 1) * (n + 1) + (n + m + 2 + 1) / 2;
+}
+// DenseKeepIn: DenseIn whose epilogue stores the final state (`keep`; dlp_batch_create_dense).
+// ResIn: the resident state itself, continued and stored again (dlp_batch_resolve); with c != NULL
+// the prologue first rebuilds LP k's objective row from c + k * sc by the rule of
+// dlp_session_set_objective, fused into the one read of the tableau.
+struct DenseKeepIn : DenseIn {
+    static constexpr bool keep = true;
+    BatchState st;
+};
+struct ResIn {
+    static constexpr bool dense = false, resident = true, keep = true;
+    BatchState st;
+    const double* c;
+    int64_t sc;
+};
+
+// acc = acc + (cb * t): two roundings, never contracted (dlp_reopt.hip's fold step)
+__device__ __forceinline__ double fold_step(double acc, double cb, double t) {
+#pragma clang fp contract(off)
+    const double prod = cb * t;
+    return acc + prod;
+}
+typedef unsigned int u32x2 __attribute__((__vector_size__(2 * sizeof(unsigned int))));   // a b64 buffer store's data
+__device__ __forceinline__ double mul_rounded(double a, double b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ bool not_finite(double v) { return !(__builtin_fabs(v) < __builtin_inf()); }
 
 // One workgroup = one LP.  The LDS holds only the NONBASIC columns of the
 // tableau (+ the RHS): a basic variable's column is a unit vector, so storing
@@ -133,12 +176,56 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
     int32_t* var = (int32_t*)(prow + W);                // n
     int32_t* basis = var + n;                           // m
     // scratch: [0] q (variable), [1] slot of q, [2] p, [3] status, [4] bland, [5] dense: some b_i not >= 0
+    // (resident: 1 rejected at creation, 2 a c_k entry that is not finite)
     int32_t* sI = basis + m;
     double* sD = (double*)(sI + 6 + ((n + m) & 1));     // piv, ratio (8-B aligned)
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int64_t lp = blockIdx.x;
-    if constexpr (!In::dense) {
+    // the final state to the batch's resident buffers (In::keep)
+    auto store_state = [&](int stt) {
+        if constexpr (In::keep) {
+            double* __restrict__ dst = in.st.S + lp * state_doubles(m, n);
+            int32_t* __restrict__ di = (int32_t*)(dst + (m + 1) * W);
+            for (int e = tid; e < (m + 1) * W; e += blockDim.x) dst[e] = T[e];
+            for (int s = tid; s < n; s += blockDim.x) di[s] = var[s];
+            for (int i = tid; i < m; i += blockDim.x) di[n + i] = basis[i];
+            if (tid == 0) {
+                di[N] = sI[4];
+                di[N + 1] = stt;
+            }
+        }
+    };
+    bool has_c = false;   // (resident) a new objective: the rows are read by the fold below
+    if constexpr (In::resident) {
+        const double* __restrict__ src = in.st.S + lp * state_doubles(m, n);
+        const int32_t* __restrict__ si = (const int32_t*)(src + (m + 1) * W);
+        has_c = in.c != nullptr;
+        for (int s = tid; s < n; s += blockDim.x) var[s] = si[s];
+        for (int i = tid; i < m; i += blockDim.x) basis[i] = si[n + i];
+        if (!has_c)
+            for (int e = tid; e < (m + 1) * W; e += blockDim.x) T[e] = src[e];
+        if (wid == 0) {
+            // 1: rejected at creation; 2: a c_k entry that is not finite (this call only)
+            int bad = si[N + 1] == DLP_ERR_ARG ? 1 : 0;
+            if (has_c) {
+                const double* __restrict__ c = in.c + lp * in.sc;
+                bool nf = false;
+                for (int j = lane; j < n; j += 64) nf |= not_finite(c[j]);
+                if (__ballot(nf) != 0 && bad == 0) bad = 2;
+                // cB_i, staged where the entering column will live
+                for (int i = lane; i < m; i += 64) {
+                    const int bv = si[n + i];
+                    colq[i] = bv < n ? c[bv] : 0.0;
+                }
+            }
+            if (lane == 0) {
+                sI[5] = bad;
+                sI[3] = has_c ? (int)DLP_RUNNING : si[N + 1];
+                sI[4] = has_c ? (pricing == DLP_PRICING_BLAND ? 1 : 0) : si[N];
+            }
+        }
+    } else if constexpr (!In::dense) {
         const double* __restrict__ src = in.T + lp * (m + 1) * in.ld;
         for (int i = 0; i <= m; ++i)
             for (int s = tid; s < W; s += blockDim.x) T[i * W + s] = src[(int64_t)i * in.ld + (s < n ? s : N)];
@@ -156,32 +243,71 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
             if (lane == 0) sI[5] = anyb != 0 ? 1 : 0;
         }
     }
-    for (int s = tid; s < n; s += blockDim.x) var[s] = s;
-    for (int i = tid; i < m; i += blockDim.x) basis[i] = n + i;
-    if (tid == 0) {
-        sI[3] = DLP_RUNNING;
-        sI[4] = pricing == DLP_PRICING_BLAND ? 1 : 0;
+    if constexpr (!In::resident) {
+        for (int s = tid; s < n; s += blockDim.x) var[s] = s;
+        for (int i = tid; i < m; i += blockDim.x) basis[i] = n + i;
+        if (tid == 0) {
+            sI[3] = DLP_RUNNING;
+            sI[4] = pricing == DLP_PRICING_BLAND ? 1 : 0;
+        }
     }
     __syncthreads();
-    if constexpr (In::dense) {
+    if constexpr (In::dense || In::resident) {
         if (sI[5]) {   // (uniform) DLP_ERR_ARG, no pivots, the slack basis, NaN values
             const double nan = __builtin_nan("");
+            const bool resident_basis = In::resident && sI[5] == 2;   // a bad c_k: the basis as it stands
             if (tid == 0) {
                 if (out.status) out.status[lp] = DLP_ERR_ARG;
                 if (out.npivots) out.npivots[lp] = 0;
                 if (out.objective) out.objective[lp] = nan;
             }
             if (out.basis)
-                for (int i = tid; i < m; i += blockDim.x) out.basis[lp * m + i] = n + i;
+                for (int i = tid; i < m; i += blockDim.x) out.basis[lp * m + i] = resident_basis ? basis[i] : n + i;
             if (out.x)
                 for (int j = tid; j < n; j += blockDim.x) out.x[lp * n + j] = nan;
             if (out.y)
                 for (int i = tid; i < m; i += blockDim.x) out.y[lp * m + i] = nan;
+            // a fresh batch keeps the rejected LP as loaded, marked DLP_ERR_ARG; a resident one
+            // is left exactly as it was
+            if constexpr (!In::resident) store_state(DLP_ERR_ARG);
             return;
+        }
+    }
+    if constexpr (In::resident) {
+        if (has_c) {
+            // The objective rebuild fused into the load (dlp.h, dlp_session_set_objective's rule):
+            // a slot loop owns a column, copies its m constraint entries from the state into the
+            // LDS and folds them in row order, 8 loads requested ahead of the 8 dependent adds.
+            const double* __restrict__ src = in.st.S + lp * state_doubles(m, n);
+            const double* __restrict__ c = in.c + lp * in.sc;
+            for (int s = tid; s < W; s += blockDim.x) {
+                double acc = 0.0;
+                if (s < n && var[s] < n) acc = -c[var[s]];
+                for (int i0 = 0; i0 < m; i0 += 8) {
+                    double t[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) t[u] = src[(int64_t)min(i0 + u, m - 1) * W + s];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const int i = i0 + u;
+                        if (i < m) {
+                            T[i * W + s] = t[u];
+                            const double cb = colq[i];
+                            if (cb != 0.0) acc = fold_step(acc, cb, t[u]);
+                        }
+                    }
+                }
+                T[m * W + s] = acc;
+            }
+            __syncthreads();
         }
     }
 
     int64_t k = 0;
+    if constexpr (In::resident) {
+        // resumed without a new objective: an optimal or unbounded LP does no pivot
+        if (sI[3] == DLP_OK || sI[3] == DLP_UNBOUNDED) max_pivots = 0;
+    }
     for (; k < max_pivots; ++k) {
         // ---- a1 pricing (wave 0): lexicographic (z, variable) min + first variable < -tol
         if (wid == 0) {
@@ -313,13 +439,15 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
         if (tid == 0 && out.logs && k < out.log_cap)
             out.logs[lp * out.log_cap + k].objective = T[m * W + n];
     }
+    int stt = DLP_RUNNING;   // (thread 0's is the status)
     if (tid == 0) {
-        int stt = sI[3];
+        stt = sI[3];
         if (stt == DLP_RUNNING) stt = DLP_PIVOT_LIMIT;
         if (out.status) out.status[lp] = stt;
         if (out.npivots) out.npivots[lp] = k;
         if (out.objective) out.objective[lp] = T[m * W + n];
     }
+    store_state(stt);
     if (out.basis)
         for (int i = tid; i < m; i += blockDim.x) out.basis[lp * m + i] = basis[i];
     // x and y from the tableau as it stands, every index written exactly once (no zero fill):
@@ -526,6 +654,21 @@ __device__ __forceinline__ void move_if_row(double& dst, double src, int p) {
         : [s] "v"(src), [p] "s"(p), [row] "n"(ROW)
         : "scc");
 }
+// acc := acc + (cb * t), the product rounded, then the sum (fold_step's two roundings), cb
+// uniform in an SGPR pair.  In asm so that a step holds one temporary: left to the scheduler,
+// the 64 independent products were computed ahead of the dependent adds and the register rows
+// spilled.
+__device__ __forceinline__ void fold_row(double& acc, double cb, double t) {
+    double p;
+    // (s_nop 1: cb was written by v_readlane, and a VALU read of an SGPR a VALU wrote needs two
+    // wait states, which the compiler's hazard recognizer does not insert inside asm)
+    asm volatile(
+        "s_nop 1\n\t"
+        "v_mul_f64 %[p], %[cb], %[t]\n\t"
+        "v_add_f64 %[acc], %[acc], %[p]"
+        : [acc] "+v"(acc), [p] "=&v"(p)
+        : [cb] "s"(cb), [t] "v"(t));
+}
 template <int M, int NW, class In>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) void batched_reg_kernel(In in, int n,
                                                            int64_t max_pivots, int pricing, double tol_dj,
@@ -539,7 +682,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
     __shared__ int32_t s_p, s_leave, s_bland;
     __shared__ double s_piv;
     __shared__ uint64_t s_zm;   // rows 0..63 of the entering column that are +-0 (the elimination's skip rule)
-    __shared__ int32_t s_bad;   // dense input: some b_i is not >= 0
+    __shared__ int32_t s_bad;   // dense input: some b_i is not >= 0 (resident: 1 rejected at creation, 2 a bad c_k)
+    __shared__ double s_cb[M];  // resident, new objective: cB_i = c[basis[i]] (+0.0 for a slack)
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int N = n + M;
     const int sl = tid;              // this lane's slot: < n a variable's column
@@ -556,7 +700,71 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
     // bits): the RHS column needs no slot of its own, so n columns take ceil(n / 64) waves (round
     // 4: 64 x 128 in 2 waves instead of 3, 64 x 64 in 1 instead of 2; more LPs per CU)
     double rr = 0.0, zr = 0.0;
-    if constexpr (!In::dense) {
+    // the final state to the batch's resident buffers (In::keep): the loads' pattern as stores,
+    // lanes past the slots out of range (dropped)
+    auto store_state = [&](int stt) __attribute__((always_inline)) {
+        if constexpr (In::keep) {
+            // (W opaque: the 65 row offsets are computed again here, not kept in SGPRs across the
+            // pivot loop from the resident prologue's loads, where they would spill)
+            int W = n + 1;
+            asm volatile("" : "+s"(W));
+            double* const rec = in.st.S + lp * state_doubles(M, n);
+            const __amdgpu_buffer_rsrc_t rs =
+                __builtin_amdgcn_make_buffer_rsrc((void*)rec, (short)0, R * W * 8, 0x00020000);
+            each<R>([&](auto I) {
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, t[I]), rs, voff, (int)I * W * 8, 0);
+            });
+            if (wid == 0) {
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, rr), rs, (lane * W + n) * 8, 0, 0);
+                if (lane == 0)
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, zr), rs, (M * W + n) * 8, 0, 0);
+            }
+            int32_t* __restrict__ di = (int32_t*)(rec + R * W);
+            if (own) di[sl] = var;
+            for (int i = tid; i < M; i += blockDim.x) di[n + i] = s_basis[i];
+            if (tid == 0) {
+                di[N] = s_bland;
+                di[N + 1] = stt;
+            }
+        }
+    };
+    bool has_c = false;   // (resident) a new objective
+    int saved = DLP_RUNNING;
+    double acc = 0.0;     // (resident, has_c) this slot's fold, started at -c[var]
+    if constexpr (In::resident) {
+        // the state's loads: GenIn's pattern with row stride W = n + 1 and the RHS at slot n
+        const int W = n + 1;
+        const double* const rec = in.st.S + lp * state_doubles(M, n);
+        const __amdgpu_buffer_rsrc_t rs =
+            __builtin_amdgcn_make_buffer_rsrc((void*)rec, (short)0, R * W * 8, 0x00020000);
+        each<R>([&](auto I) {
+            t[I] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, (int)I * W * 8, 0));
+        });
+        const int32_t* __restrict__ si = (const int32_t*)(rec + R * W);
+        if (own) var = si[sl];
+        saved = si[N + 1];
+        has_c = in.c != nullptr;
+        if (wid == 0) {
+            rr = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, (lane * W + n) * 8, 0, 0));
+            zr = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, (M * W + n) * 8, 0, 0));
+            const int bv = si[n + lane];
+            s_basis[lane] = bv;
+            // 1: rejected at creation; 2: a c_k entry that is not finite (this call only)
+            int bad = saved == DLP_ERR_ARG ? 1 : 0;
+            if (has_c) {
+                const double* __restrict__ c = in.c + lp * in.sc;
+                bool nf = false;
+                for (int j = lane; j < n; j += 64) nf |= not_finite(c[j]);
+                if (__ballot(nf) != 0 && bad == 0) bad = 2;
+                s_cb[lane] = bv < n ? c[bv] : 0.0;   // cB_i, staged once per LP
+            }
+            if (lane == 0) {
+                s_bad = bad;
+                s_bland = has_c ? (pricing == DLP_PRICING_BLAND ? 1 : 0) : si[N];
+            }
+        }
+        if (has_c && own && var < n) acc = -in.c[lp * in.sc + var];
+    } else if constexpr (!In::dense) {
         const int64_t ldg = in.ld;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
             (void*)(in.T + lp * (int64_t)R * ldg), (short)0, (int)((int64_t)R * ldg * 8), 0x00020000);
@@ -586,25 +794,56 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
             if (lane == 0) s_bad = anyb != 0 ? 1 : 0;
         }
     }
-    for (int i = tid; i < M; i += blockDim.x) s_basis[i] = n + i;
-    if (tid == 0) s_bland = pricing == DLP_PRICING_BLAND ? 1 : 0;
+    if constexpr (!In::resident) {
+        for (int i = tid; i < M; i += blockDim.x) s_basis[i] = n + i;
+        if (tid == 0) s_bland = pricing == DLP_PRICING_BLAND ? 1 : 0;
+    }
     __syncthreads();
-    if constexpr (In::dense) {
+    if constexpr (In::dense || In::resident) {
         if (s_bad) {   // (uniform) DLP_ERR_ARG, no pivots, the slack basis, NaN values
             const double nan = __builtin_nan("");
+            const bool resident_basis = In::resident && s_bad == 2;   // a bad c_k: the basis as it stands
             if (tid == 0) {
                 if (out.status) out.status[lp] = DLP_ERR_ARG;
                 if (out.npivots) out.npivots[lp] = 0;
                 if (out.objective) out.objective[lp] = nan;
             }
             if (out.basis)
-                for (int i = tid; i < M; i += blockDim.x) out.basis[lp * M + i] = n + i;
+                for (int i = tid; i < M; i += blockDim.x) out.basis[lp * M + i] = resident_basis ? s_basis[i] : n + i;
             if (out.x && own) out.x[lp * n + sl] = nan;
             if (out.y && wid == 0) out.y[lp * M + lane] = nan;
+            // a fresh batch keeps the rejected LP as loaded, marked DLP_ERR_ARG; a resident one
+            // is left exactly as it was
+            if constexpr (!In::resident) store_state(DLP_ERR_ARG);
             return;
         }
     }
     int status = DLP_RUNNING;
+    if constexpr (In::resident) {
+        if (has_c) {
+            // The objective rebuild, on the rows just loaded (dlp.h, dlp_session_set_objective's
+            // rule): the lane owns its slot's column and folds rows 0..M-1 ascending, cB_i from
+            // lane i's register by v_readlane (uniform: a skipped row is a scalar branch).
+            const double cbv = s_cb[lane];
+            // (the objective value: the same fold of the RHS, wave 0's lane i holding row i's
+            // product, added in row order)
+            const double prod = mul_rounded(cbv, rr);
+            double z = 0.0;
+            each<M>([&](auto I) {
+                const double cb = readlane_f64(cbv, (int)I);
+                if (cb != 0.0) {
+                    fold_row(acc, cb, t[I]);
+                    if (wid == 0) z = z + readlane_f64(prod, (int)I);
+                }
+            });
+            t[M] = acc;
+            if (wid == 0) zr = z;
+        } else if (saved == DLP_OK || saved == DLP_UNBOUNDED) {
+            // resumed without a new objective: an optimal or unbounded LP does no pivot
+            status = saved;
+            max_pivots = 0;
+        }
+    }
     int64_t k = 0;
     auto stamp = [&](int ph) {
         if (out.stamps && lp == 0 && tid == 0 && k < 64) out.stamps[k * 8 + ph] = wall_clock64();
@@ -763,6 +1002,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
         if (out.npivots) out.npivots[lp] = k;
         if (out.objective) out.objective[lp] = zr;
     }
+    store_state(status == DLP_RUNNING ? (int)DLP_PIVOT_LIMIT : status);
     if (out.basis)
         for (int i = tid; i < M; i += blockDim.x) out.basis[lp * M + i] = s_basis[i];
     // x and y from the tableau as it stands, every index written exactly once (no zero fill):
@@ -842,6 +1082,18 @@ struct DeviceGuard {
     ~DeviceGuard() { if (dev >= 0) (void)hipSetDevice(dev); }
 };
 }  // namespace
+
+// A resident batch (dlp_batch_create_dense): its shape and options, its own context (stream,
+// events, output buffers) and the state buffers of dlp::BatchState plus the staging buffer of
+// host objectives.  They belong to the handle: dlp_release_cached_memory does not see them.
+struct dlp_batch {
+    int64_t nlp = 0, m = 0, n = 0;
+    dlp_options opt{};
+    BatchCtx ctx;
+    void *dS = nullptr, *dC = nullptr;   // the state records (dlp::BatchState), host objectives staged
+    int64_t bytes = 0;
+    bool reg = false;
+};
 
 namespace dlp {
 // Free the cached batch contexts of `device` (-1: all); returns the device bytes freed.
@@ -923,8 +1175,16 @@ struct BatchJob {
     int64_t nlp, m, n;
     int kind;
     uint64_t seed;
-    const dlp_batch_dense_in* din;   // NULL: generated
+    const dlp_batch_dense_in* din;   // NULL: generated (or, with `resolve`, the resident state)
     dlp_batch_out out;
+    // a resident batch (dlp_batch_*): its own context instead of the device's cached one; the
+    // dense kernels keep the final state in it (creation), or continue from it (resolve, with
+    // the new objectives rc: NULL = resume)
+    dlp_batch* batch;
+    bool resolve;
+    const double* rc;
+    int64_t rstride;
+    int rc_device;
 };
 
 int batched_run(const dlp_options& o, const BatchJob& job) {
@@ -959,7 +1219,10 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
     BatchCtx priv;
     BatchCtx* c = &priv;
     std::unique_lock<std::mutex> lk;
-    if (o.device < kBatchDevs) {
+    dlp_batch* const bt = job.batch;
+    if (bt) {
+        c = &bt->ctx;   // (a handle is not thread-safe: no lock)
+    } else if (o.device < kBatchDevs) {
         lk = std::unique_lock<std::mutex>(g_batch_mu[o.device], std::try_to_lock);
         if (lk.owns_lock()) c = &g_batch[o.device];
     }
@@ -980,7 +1243,7 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
     if (!c->s) HIP_BTRY(hipStreamCreateWithFlags(&c->s, hipStreamNonBlocking));
     if (!c->e0) HIP_BTRY(hipEventCreate(&c->e0));
     if (!c->e1) HIP_BTRY(hipEventCreate(&c->e1));
-    if (!din) HIP_BTRY(ensure_buf(&c->dT, &c->capT, sizeof(double) * nlp * (m + 1) * ldg));
+    if (!din && !job.resolve) HIP_BTRY(ensure_buf(&c->dT, &c->capT, sizeof(double) * nlp * (m + 1) * ldg));
     if (stage) HIP_BTRY(ensure_buf(&c->dIn, &c->capIn, sizeof(double) * (cntA + cntb + cntc)));
     HIP_BTRY(ensure_buf(&c->dOut, &c->capOut, bOut));
     HIP_BTRY(ensure_buf(&c->hOut, &c->capH, bOut, true));
@@ -991,11 +1254,38 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
     dObj = (double*)c->dOut;
     dNp = (int64_t*)(dObj + nlp);
     dSt = (int32_t*)(dNp + nlp);
+    if (bt && !job.resolve) {
+        // the resident state (and the staging buffer of host objectives), owned by the handle
+        const size_t bS = sizeof(double) * nlp * dlp::state_doubles(m, n), bC = sizeof(double) * nlp * n;
+        if (hipMalloc(&bt->dS, bS) != hipSuccess || hipMalloc(&bt->dC, bC) != hipSuccess) {
+            (void)hipGetLastError();
+            dlp::set_error(who + ": the batch's resident state does not fit in device memory");
+            rc = DLP_ERR_OOM;
+            goto done;
+        }
+        bt->bytes = (int64_t)(bS + bC);
+    }
     {
         hipStream_t s = c->s;
         dlp::GenIn gin{(const double*)c->dT, ldg};
         dlp::DenseIn dn{};
-        if (!din) {
+        dlp::BatchState bst{bt ? (double*)bt->dS : nullptr};
+        dlp::ResIn rin{bst, nullptr, 0};
+        if (job.resolve) {
+            if (job.rc && !job.rc_device) {   // host objectives: packed into the handle's staging buffer
+                const size_t per = sizeof(double) * n;
+                if (job.rstride == 0 || job.rstride == n)
+                    HIP_BTRY(hipMemcpyAsync(bt->dC, job.rc, per * (job.rstride ? nlp : 1), hipMemcpyHostToDevice, s));
+                else
+                    HIP_BTRY(hipMemcpy2DAsync(bt->dC, per, job.rc, sizeof(double) * job.rstride, per, (size_t)nlp,
+                                              hipMemcpyHostToDevice, s));
+                rin.c = (const double*)bt->dC;
+                rin.sc = job.rstride ? n : 0;
+            } else {
+                rin.c = job.rc;
+                rin.sc = job.rstride;
+            }
+        } else if (!din) {
             dim3 gg((unsigned)((m + 1 + 3) / 4), (unsigned)nlp);
             dlp::batched_generate_kernel<<<gg, 256, 0, s>>>((double*)c->dT, ldg, m, n, job.kind, job.seed);
             HIP_BTRY(hipGetLastError());
@@ -1064,7 +1354,13 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
             }
             return hipGetLastError();
         };
-        HIP_BTRY(din ? launch(dn) : launch(gin));
+        if (job.resolve)
+            HIP_BTRY(launch(rin));
+        else if (bt)
+            HIP_BTRY(launch(dlp::DenseKeepIn{dn, bst}));
+        else
+            HIP_BTRY(din ? launch(dn) : launch(gin));
+        if (bt) bt->reg = reg;
         HIP_BTRY(hipEventRecord(c->e1, s));
         // read back only what the caller asked for: the packed outputs it wants in one copy
         // (objective | pivot counts | status are contiguous), basis, logs, x and y when requested
@@ -1145,4 +1441,117 @@ extern "C" int dlp_batched_solve_dense(int64_t nlp, int64_t m, int64_t n, const 
     job.din = in;
     job.out = *out;
     return batched_run(o, job);
+}
+
+// ---- resident batches
+namespace {
+void batch_destroy(dlp_batch* b) {
+    DeviceGuard guard;
+    if (b->opt.device >= 0) (void)hipSetDevice(b->opt.device);
+    b->ctx.free_all();   // (drains the stream first)
+    for (void* p : {b->dS, b->dC})
+        if (p) (void)hipFree(p);
+    (void)hipGetLastError();
+    delete b;
+}
+}  // namespace
+
+extern "C" int dlp_batch_create_dense(int64_t nlp, int64_t m, int64_t n, const dlp_batch_dense_in* in,
+                                      const dlp_options* opt, const dlp_batch_out* out, dlp_batch** batch) {
+    dlp_options o;
+    if (opt) o = *opt; else dlp_options_default(&o);
+    if (batch) *batch = nullptr;
+    const auto bad_stride = [](int64_t s, int64_t need) { return s != 0 && s < need; };
+    if (nlp <= 0 || m <= 0 || n <= 0 || nlp > 65535 * 16 || !in || !batch || (out && out->log_cap < 0) || !in->A ||
+        !in->b || !in->c || (in->device != 0 && in->device != 1) || bad_stride(in->strideA, m * n) ||
+        bad_stride(in->strideb, m) || bad_stride(in->stridec, n)) {
+        dlp::set_error("dlp_batch_create_dense: bad arguments");
+        return DLP_ERR_ARG;
+    }
+    dlp_batch* b = new (std::nothrow) dlp_batch;
+    if (!b) return DLP_ERR_OOM;
+    b->nlp = nlp; b->m = m; b->n = n;
+    b->opt = o;
+    BatchJob job{};
+    job.who = "dlp_batch_create_dense";
+    job.nlp = nlp; job.m = m; job.n = n;
+    job.din = in;
+    if (out) job.out = *out;
+    job.batch = b;
+    const int rc = batched_run(o, job);
+    if (rc != DLP_OK) {
+        b->opt.device = rc == DLP_ERR_NODEVICE || rc == DLP_ERR_ARG ? -1 : b->opt.device;
+        batch_destroy(b);
+        return rc;
+    }
+    *batch = b;
+    return DLP_OK;
+}
+
+extern "C" int dlp_batch_resolve(dlp_batch* batch, const double* c, int64_t stridec, int c_is_device,
+                                 int64_t max_pivots, const dlp_batch_out* out) {
+    if (!batch || max_pivots < 0 || (out && out->log_cap < 0) ||
+        (c && ((stridec != 0 && stridec < batch->n) || (c_is_device != 0 && c_is_device != 1)))) {
+        dlp::set_error("dlp_batch_resolve: bad arguments");
+        return DLP_ERR_ARG;
+    }
+    dlp_options o = batch->opt;
+    o.max_pivots = max_pivots;
+    BatchJob job{};
+    job.who = "dlp_batch_resolve";
+    job.nlp = batch->nlp; job.m = batch->m; job.n = batch->n;
+    if (out) job.out = *out;
+    job.batch = batch;
+    job.resolve = true;
+    job.rc = c;
+    job.rstride = stridec;
+    job.rc_device = c_is_device;
+    return batched_run(o, job);
+}
+
+extern "C" int dlp_batch_read(dlp_batch* batch, int64_t k, double* T, int32_t* basis) {
+    if (!batch || k < 0 || k >= batch->nlp) {
+        dlp::set_error("dlp_batch_read: bad arguments");
+        return DLP_ERR_ARG;
+    }
+    const int64_t m = batch->m, n = batch->n, N = n + m, W = n + 1, ld = dlp_tableau_ld(m, n);
+    std::vector<double> t((size_t)dlp::state_doubles(m, n));
+    const int32_t* const si = (const int32_t*)(t.data() + (m + 1) * W);
+    DeviceGuard guard;
+    if (hipSetDevice(batch->opt.device) != hipSuccess ||
+        hipMemcpy(t.data(), (const double*)batch->dS + k * dlp::state_doubles(m, n), sizeof(double) * t.size(),
+                  hipMemcpyDeviceToHost) != hipSuccess) {
+        dlp::set_error(std::string("dlp_batch_read: ") + hipGetErrorString(hipGetLastError()));
+        return DLP_ERR_HIP;
+    }
+    if (basis) std::memcpy(basis, si + n, sizeof(int32_t) * m);
+    if (T) {
+        // the full layout: slot s is the column of var[s], a basic variable's column the unit
+        // vector of its row (objective entry +0.0), the RHS at column N, padding +0.0
+        std::fill(T, T + (m + 1) * ld, 0.0);
+        for (int64_t i = 0; i <= m; ++i) {
+            for (int64_t s = 0; s < n; ++s) T[i * ld + si[s]] = t[i * W + s];
+            T[i * ld + N] = t[i * W + n];
+        }
+        for (int64_t i = 0; i < m; ++i) T[i * ld + si[n + i]] = 1.0;
+    }
+    return DLP_OK;
+}
+
+extern "C" int dlp_batch_info(const dlp_batch* batch, int64_t* nlp, int64_t* m, int64_t* n,
+                              int32_t* register_kernel, int64_t* device_bytes) {
+    if (!batch) {
+        dlp::set_error("dlp_batch_info: bad arguments");
+        return DLP_ERR_ARG;
+    }
+    if (nlp) *nlp = batch->nlp;
+    if (m) *m = batch->m;
+    if (n) *n = batch->n;
+    if (register_kernel) *register_kernel = batch->reg ? 1 : 0;
+    if (device_bytes) *device_bytes = batch->bytes;
+    return DLP_OK;
+}
+
+extern "C" void dlp_batch_free(dlp_batch* batch) {
+    if (batch) batch_destroy(batch);
 }

@@ -517,15 +517,9 @@ def batched_solve(nlp: int, m: int, n: int, seed: int, degenerate: bool = False,
     return BatchResult(obj, st, npv, basis, logs, ms.value)
 
 
-def batched_solve_dense(A, b, c, *, want_x: bool = True, want_y: bool = True, want_basis: bool = False,
-                        log_cap: int = 0, **opts) -> BatchResult:
-    """dlp_batched_solve_dense: the caller's own LPs max c_k^T x s.t. A_k x <= b_k, x >= 0
-    (b_k >= 0), all m x n, one workgroup each.  A is (nlp, m, n) or (m, n), b (nlp, m) or (m,),
-    c (nlp, n) or (n,); an unbatched argument is shared by every LP.  numpy arrays are copied to
-    the device on every call; torch float64 tensors on device ``opts.get("device", 0)`` are read
-    in place (pass those when the data is already on the GPU: the copy costs more than the
-    solve).  An LP with a negative or NaN b_i gets status ERR_ARG and NaN objective, x and y;
-    the others are solved."""
+def _batch_dense_inputs(A, b, c, opts):
+    """The arrays of batched_solve_dense / Batch: validated, made contiguous, described by a
+    BatchDenseIn.  Returns (nlp, m, n, din, arrays kept alive for the call)."""
     args = (A, b, c)
     on_dev = [hasattr(v, "data_ptr") for v in args]
     if any(on_dev) and not all(on_dev):
@@ -554,9 +548,13 @@ def batched_solve_dense(A, b, c, *, want_x: bool = True, want_y: bool = True, wa
     if len(lead) > 1 or 0 in lead:
         raise ValueError(f"inconsistent batch dimensions: A {sA}, b {sb}, c {sc}")
     nlp = lead.pop() if lead else 1
-    o = options(**opts)
     din = L.BatchDenseIn(ptrs[0], ptrs[1], ptrs[2], m * n if len(sA) == 3 else 0,
                          m if len(sb) == 2 else 0, n if len(sc) == 2 else 0, 1 if all(on_dev) else 0, 0)
+    return nlp, m, n, din, (A, b, c)
+
+
+def _batch_outputs(nlp, m, n, want_x, want_y, want_basis, log_cap):
+    """Host output arrays and the BatchOut naming them; result() builds the BatchResult."""
     obj = np.zeros(nlp)
     st = np.zeros(nlp, np.int32)
     npv = np.zeros(nlp, np.int64)
@@ -571,9 +569,123 @@ def batched_solve_dense(A, b, c, *, want_x: bool = True, want_y: bool = True, wa
                      logs.ctypes.data_as(C.POINTER(L.Pivot)) if logs is not None else None, log_cap,
                      _dptr(x) if x is not None else None, _dptr(y) if y is not None else None,
                      C.pointer(ms))
+    return out, lambda: BatchResult(obj, st, npv, basis, logs, ms.value, x, y)
+
+
+def batched_solve_dense(A, b, c, *, want_x: bool = True, want_y: bool = True, want_basis: bool = False,
+                        log_cap: int = 0, **opts) -> BatchResult:
+    """dlp_batched_solve_dense: the caller's own LPs max c_k^T x s.t. A_k x <= b_k, x >= 0
+    (b_k >= 0), all m x n, one workgroup each.  A is (nlp, m, n) or (m, n), b (nlp, m) or (m,),
+    c (nlp, n) or (n,); an unbatched argument is shared by every LP.  numpy arrays are copied to
+    the device on every call; torch float64 tensors on device ``opts.get("device", 0)`` are read
+    in place (pass those when the data is already on the GPU: the copy costs more than the
+    solve).  An LP with a negative or NaN b_i gets status ERR_ARG and NaN objective, x and y;
+    the others are solved."""
+    nlp, m, n, din, _keep = _batch_dense_inputs(A, b, c, opts)
+    o = options(**opts)
+    out, result = _batch_outputs(nlp, m, n, want_x, want_y, want_basis, log_cap)
     L.check(L.lib().dlp_batched_solve_dense(nlp, m, n, C.byref(din), C.byref(o), C.byref(out)),
             "dlp_batched_solve_dense")
-    return BatchResult(obj, st, npv, basis, logs, ms.value, x, y)
+    return result()
+
+
+class Batch:
+    """A resident batch (dlp_batch_*): the LPs of batched_solve_dense solved once and kept on
+    the device, then re-optimised from each LP's current basis whenever the objectives change
+    (the reference's loop over its subproblems: same constraints, new weights, every
+    iteration).  A, b, c, the output switches and **opts are batched_solve_dense's; ``result``
+    is the cold solve's BatchResult.  A handle is not thread-safe."""
+
+    def __init__(self, A, b, c, *, want_x: bool = True, want_y: bool = True, want_basis: bool = False,
+                 log_cap: int = 0, **opts):
+        self._h = C.c_void_p()
+        nlp, m, n, din, _keep = _batch_dense_inputs(A, b, c, opts)
+        self.nlp, self.m, self.n = nlp, m, n
+        self.device = int(opts.get("device", 0))
+        o = options(**opts)
+        self.max_pivots = int(o.max_pivots)
+        out, result = _batch_outputs(nlp, m, n, want_x, want_y, want_basis, log_cap)
+        h = C.c_void_p()
+        L.check(L.lib().dlp_batch_create_dense(nlp, m, n, C.byref(din), C.byref(o), C.byref(out), C.byref(h)),
+                "dlp_batch_create_dense")
+        self._h = h
+        self.result = result()
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the batch is closed")
+        return self._h
+
+    def resolve(self, c=None, *, max_pivots: int | None = None, want_x: bool = True, want_y: bool = True,
+                want_basis: bool = False, log_cap: int = 0) -> BatchResult:
+        """dlp_batch_resolve: continue every LP from its resident basis, for up to max_pivots
+        more pivots each (default: the max_pivots of creation).  c: new objectives, (nlp, n) or
+        (n,) for one shared by every LP, a numpy array or a float64 tensor on the batch's
+        device; None resumes with the objectives as they stand.  An LP whose c_k has a NaN or
+        inf entry reports ERR_ARG for this call and is left as it was."""
+        ptr, stride, on_dev = None, 0, 0
+        if c is not None:
+            if hasattr(c, "data_ptr"):
+                import torch
+                if c.dtype != torch.float64:
+                    raise ValueError(f"c must be a float64 tensor, not {c.dtype}")
+                if c.device.type != "cuda" or c.device.index != self.device:
+                    raise ValueError(f"c is on {c.device}, the batch lives on device {self.device}")
+                shape = tuple(c.shape)
+            else:
+                c = np.asarray(c)
+                if c.dtype.kind not in "fiu":
+                    raise ValueError(f"c must be real-valued (float64), not {c.dtype}")
+                shape = c.shape
+            if shape not in ((self.nlp, self.n), (self.n,)):
+                raise ValueError(f"c must have shape ({self.nlp}, {self.n}) or ({self.n},), not {shape}")
+            if hasattr(c, "data_ptr"):
+                c = c.contiguous()
+                torch.cuda.current_stream(self.device).synchronize()   # c is complete before the call
+                ptr, on_dev = c.data_ptr(), 1
+            else:
+                c = np.ascontiguousarray(c, dtype=np.float64)
+                ptr = c.ctypes.data
+            stride = self.n if len(shape) == 2 else 0
+        budget = self.max_pivots if max_pivots is None else int(max_pivots)
+        if budget < 0:
+            raise ValueError("max_pivots must be >= 0")
+        out, result = _batch_outputs(self.nlp, self.m, self.n, want_x, want_y, want_basis, log_cap)
+        L.check(L.lib().dlp_batch_resolve(self._handle(), ptr, stride, on_dev, budget, C.byref(out)), "dlp_batch_resolve")
+        return result()
+
+    def read(self, k: int):
+        """dlp_batch_read: LP k's resident tableau in the full layout ((m+1) x tableau_ld(m, n),
+        objective row last) and its basis."""
+        T = np.zeros((self.m + 1, tableau_ld(self.m, self.n)))
+        basis = np.zeros(self.m, np.int32)
+        L.check(L.lib().dlp_batch_read(self._handle(), int(k), _dptr(T), basis.ctypes.data_as(C.POINTER(C.c_int32))),
+                "dlp_batch_read")
+        return T, basis
+
+    def info(self) -> dict:
+        nlp, m, n, db, reg = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int32()
+        L.check(L.lib().dlp_batch_info(self._handle(), C.byref(nlp), C.byref(m), C.byref(n), C.byref(reg),
+                                       C.byref(db)), "dlp_batch_info")
+        return {"nlp": nlp.value, "m": m.value, "n": n.value, "register_kernel": bool(reg.value),
+                "device_bytes": db.value}
+
+    def close(self):
+        if self._h:
+            L.lib().dlp_batch_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def batched_occupancy(m: int, n: int, device: int = 0) -> dict:

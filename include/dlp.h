@@ -21,6 +21,9 @@
  *   AllocationMW::RunAllocationMW: the same            dlp_session_set_objective + dlp_session_run
  *     constraints re-weighted and solved again on      (warm re-solve from the resident basis
  *     every iteration  R/allocation_mw.cpp:271-326     instead of a cold one)
+ *   the same loop over all the per-impression          dlp_batch_create_dense once, then per
+ *     subproblems  R/global_problem.cpp:270-274         iteration dlp_batch_resolve(new weights):
+ *     re-weighted by R/allocation_mw.cpp:271-326       every LP warm from its resident basis
  *   Instance::solution_ (private, no getter)           dlp_result_x / dlp_result_y
  *     R/instance.h:34
  *   "Dual Value" stdout  R/global_problem.cpp:320-322  dlp_result_objective
@@ -340,7 +343,7 @@ int dlp_session_step_update(dlp_session* s);
  * created with nranks > 1 or an RCCL id; DLP_ERR_STATE: a failed session, or a caller-driven step
  * in progress (step_candidate done, step_update not yet).
  * Not covered: changes of b or A (they need a dual simplex), a device-pointer c, multi-rank
- * sessions, general LPs, the batched API. */
+ * sessions, general LPs.  (Batches: dlp_batch_resolve applies this rule to every resident LP.) */
 int dlp_session_set_objective(dlp_session* s, const double* c, int64_t n, double* kernel_ms);
 int dlp_session_buffer(dlp_session* s, int which, void** dev_ptr, size_t* bytes);
 /* Synchronous host copies of an exchange buffer (for host-side communicators). */
@@ -544,6 +547,57 @@ int dlp_batched_solve_dense(int64_t nlp, int64_t m, int64_t n, const dlp_batch_d
  * n <= 192) or the LDS one.  C5 is bound by per-pivot serial latency x this residency. */
 int dlp_batched_occupancy(int64_t m, int64_t n, int device, int32_t* lps_per_cu,
                           int32_t* threads_per_lp, int32_t* register_kernel);
+
+/* ---- resident batch: re-solve the same LPs after new objectives --------
+ * The reference re-weights the objective of all its per-impression subproblems on every
+ * iteration (R/allocation_mw.cpp:271-326 over R/global_problem.cpp:270-274).  A dlp_batch keeps
+ * every LP's final state (condensed tableau, basis, Bland flag, status) on the device between
+ * calls, so an iteration re-optimises each LP from its current basis instead of solving it
+ * cold, and A is uploaded once.  Every LP stays bit-identical to the single-LP path: a cold
+ * dlp_solve, then dlp_session_set_objective + dlp_session_run.
+ *
+ * Rejected LPs: an LP rejected at creation (some b_i not >= 0) stays DLP_ERR_ARG with NaN
+ *   objective, x and y and the slack basis in every later call.
+ * Non-finite c_k: a c_k with an entry that is not finite makes that LP alone report
+ *   DLP_ERR_ARG with NaN objective, x and y (0 pivots, its basis as it stands) for this call;
+ *   its resident state is left exactly as it was and the other LPs run.  The kernel checks
+ *   this, for host and device c alike (a device input cannot be checked on the host).
+ * Call-level errors are validated before anything is enqueued and leave the batch unchanged:
+ *   DLP_ERR_ARG (NULL batch, a stride that is neither 0 nor >= n, c_is_device not 0 / 1,
+ *   negative max_pivots or log_cap); at creation also DLP_ERR_OOM when the state does not fit
+ *   in device memory.
+ * max_pivots == 0 with a c rebuilds the objective rows and does no pivot: status
+ *   DLP_PIVOT_LIMIT, as every batch kernel reports a zero budget.
+ * Handles: a handle is not thread-safe.  Its state buffers belong to the handle
+ *   (dlp_batch_info's device_bytes); dlp_release_cached_memory does not touch them. */
+typedef struct dlp_batch dlp_batch;
+
+/* Cold solve exactly as dlp_batched_solve_dense (same inputs, options, outputs, per-LP
+ * DLP_ERR_ARG for a b_i that is not >= 0, same call-level errors in the same order), and keep
+ * every LP's final state on the device.  out may be NULL.  A, b and c are not read after the
+ * call returns. */
+int dlp_batch_create_dense(int64_t nlp, int64_t m, int64_t n, const dlp_batch_dense_in* in,
+                           const dlp_options* opt, const dlp_batch_out* out, dlp_batch** batch);
+/* Continue every LP from its resident basis for up to max_pivots more pivots (per LP, this call).
+ *   c != NULL: first replace LP k's objective by max c_k^T x (c_k at c + k*stridec, n doubles;
+ *     stridec 0 = one c for all LPs, else >= n; c_is_device 0 host / 1 device pointer on the
+ *     batch's device, complete when the call is made) by the rule of dlp_session_set_objective
+ *     applied to LP k's tableau, reset the Bland state as that call does, status RUNNING
+ *     whatever it was (optimal, unbounded, pivot limit).
+ *   c == NULL: resume with the objective row and Bland state as they stand; an LP that is
+ *     optimal or unbounded does 0 pivots and reports that status again.
+ * out as in dlp_batched_solve_dense (may be NULL); npivots and logs are this call's pivots;
+ * objective, x, y, basis from the tableau as it stands afterwards.  Tolerances, pricing and
+ * device are those of creation. */
+int dlp_batch_resolve(dlp_batch* batch, const double* c, int64_t stridec, int c_is_device,
+                      int64_t max_pivots, const dlp_batch_out* out);
+/* LP k's resident tableau in the full layout of dlp_session_tableau ((m+1) x dlp_tableau_ld(m,n),
+ * basic columns as exact unit vectors, their objective entries +0.0, padding +0.0) and its
+ * basis (m entries).  Either pointer may be NULL. */
+int  dlp_batch_read(dlp_batch* batch, int64_t k, double* T, int32_t* basis);
+int  dlp_batch_info(const dlp_batch* batch, int64_t* nlp, int64_t* m, int64_t* n,
+                    int32_t* register_kernel, int64_t* device_bytes);
+void dlp_batch_free(dlp_batch* batch);   /* NULL is a no-op */
 
 /* ---- multiplicative-weights path ------------------
  * The reference's own epsilon-approximate MW loop (R/allocation_mw.cpp:271-326,
