@@ -97,12 +97,12 @@ struct BatchOut {
 // condensed tableau: slot j of row i is A_k[i][j], the RHS b_k[i], the objective row -c_k[j]
 // with value +0 (the single-LP dense fill), and no full-layout copy passes through HBM.
 struct GenIn {
-    static constexpr bool dense = false, resident = false, keep = false;
+    static constexpr bool dense = false, resident = false, keep = false, dual = false;
     const double* T;
     int64_t ld;
 };
 struct DenseIn {
-    static constexpr bool dense = true, resident = false, keep = false;
+    static constexpr bool dense = true, resident = false, keep = false, dual = false;
     const double *A, *b, *c;
     int64_t sA, sb, sc;
 };
@@ -128,11 +128,27 @@ struct DenseKeepIn : DenseIn {
     BatchState st;
 };
 struct ResIn {
-    static constexpr bool dense = false, resident = true, keep = true;
+    static constexpr bool dense = false, resident = true, keep = true, dual = false;
     BatchState st;
     const double* c;
     int64_t sc;
 };
+// RhsIn: the resident state continued by the dual simplex after new right-hand sides
+// (dlp_batch_resolve_rhs): the prologue rebuilds LP k's RHS column from
+// b + k * sb by the fold of dlp.h, then the pivot loop selects the leaving row first.
+struct RhsIn {
+    static constexpr bool dense = false, resident = true, keep = true, dual = true;
+    BatchState st;
+    const double* b;
+    int64_t sb;
+    double tol_feas;
+    double* last;   // [nlp * m]: the b_k each LP's RHS column was last built from (continuation, below)
+    static constexpr const double* c = nullptr;   // (no new objective in this call)
+    static constexpr int64_t sc = 0;
+};
+// The status word of a record whose dual phase was stopped by the budget: its RHS has negative
+// entries, so only dlp_batch_resolve_rhs may continue it.  Reported outwards as DLP_PIVOT_LIMIT.
+constexpr int kDualPending = 100;
 
 // acc = acc + (cb * t): two roundings, never contracted (dlp_reopt.hip's fold step)
 __device__ __forceinline__ double fold_step(double acc, double cb, double t) {
@@ -176,7 +192,9 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
     int32_t* var = (int32_t*)(prow + W);                // n
     int32_t* basis = var + n;                           // m
     // scratch: [0] q (variable), [1] slot of q, [2] p, [3] status, [4] bland, [5] dense: some b_i not >= 0
-    // (resident: 1 rejected at creation, 2 a c_k entry that is not finite)
+    // (resident: 1 rejected at creation, 2 a c_k / b_k entry that is not finite, 3 DLP_ERR_STATE:
+    // a pending dual phase in front of a primal call, or an LP that is not dual feasible in
+    // front of a dual one)
     int32_t* sI = basis + m;
     double* sD = (double*)(sI + 6 + ((n + m) & 1));     // piv, ratio (8-B aligned)
 
@@ -194,13 +212,17 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
                 di[N] = sI[4];
                 di[N + 1] = stt;
             }
+            if constexpr (In::dual) {   // the b_k this RHS column was built from
+                const double* __restrict__ b = in.b + lp * in.sb;
+                for (int i = tid; i < m; i += blockDim.x) in.last[lp * m + i] = b[i];
+            }
         }
     };
     bool has_c = false;   // (resident) a new objective: the rows are read by the fold below
     if constexpr (In::resident) {
         const double* __restrict__ src = in.st.S + lp * state_doubles(m, n);
         const int32_t* __restrict__ si = (const int32_t*)(src + (m + 1) * W);
-        has_c = in.c != nullptr;
+        has_c = !In::dual && in.c != nullptr;
         for (int s = tid; s < n; s += blockDim.x) var[s] = si[s];
         for (int i = tid; i < m; i += blockDim.x) basis[i] = si[n + i];
         if (!has_c)
@@ -219,10 +241,40 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
                     colq[i] = bv < n ? c[bv] : 0.0;
                 }
             }
+            if constexpr (In::dual) {
+                // 2: a b_k entry that is not finite; 3: some stored slot has z < -tol_dj (the LP
+                // is not dual feasible: stopped inside a primal solve, or unbounded)
+                const double* __restrict__ b = in.b + lp * in.sb;
+                bool nf = false, neg = false;
+                for (int i = lane; i < m; i += 64) nf |= not_finite(b[i]);
+                for (int s = lane; s < n; s += 64) neg |= src[m * W + s] < -tol_dj;
+                if (__ballot(nf) != 0 && bad == 0) bad = 2;
+                if (__ballot(neg) != 0 && bad == 0) bad = 3;
+                // continuation: a pending dual phase handed the very b_k (bit for bit) it was
+                // stopped with goes on from its RHS column and Bland state as they stand, so that
+                // budgets of any size give the pivots of one unbounded call
+                bool cont = si[N + 1] == kDualPending;
+                if (cont) {
+                    const double* __restrict__ last = in.last + lp * m;
+                    bool diff = false;
+                    for (int i = lane; i < m; i += 64)
+                        diff |= __builtin_bit_cast(uint64_t, b[i]) != __builtin_bit_cast(uint64_t, last[i]);
+                    cont = __ballot(diff) == 0;
+                }
+                if (lane == 0) sI[0] = cont ? 1 : 0;
+            } else {
+                // 3: left infeasible or pending by a dual phase (negative RHS entries: the primal
+                // rule must not pivot on it)
+                const int sv = si[N + 1];
+                if (bad == 0 && (sv == DLP_INFEASIBLE || sv == kDualPending)) bad = 3;
+            }
             if (lane == 0) {
+                const bool fresh = has_c || In::dual;   // the status and the Bland state start over
                 sI[5] = bad;
-                sI[3] = has_c ? (int)DLP_RUNNING : si[N + 1];
-                sI[4] = has_c ? (pricing == DLP_PRICING_BLAND ? 1 : 0) : si[N];
+                sI[3] = fresh ? (int)DLP_RUNNING : si[N + 1];
+                sI[4] = fresh ? (pricing == DLP_PRICING_BLAND ? 1 : 0) : si[N];
+                if constexpr (In::dual)
+                    if (sI[0] && si[N]) sI[4] = 1;   // (continued: the Bland state as it was left)
             }
         }
     } else if constexpr (!In::dense) {
@@ -255,9 +307,10 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
     if constexpr (In::dense || In::resident) {
         if (sI[5]) {   // (uniform) DLP_ERR_ARG, no pivots, the slack basis, NaN values
             const double nan = __builtin_nan("");
-            const bool resident_basis = In::resident && sI[5] == 2;   // a bad c_k: the basis as it stands
+            const bool resident_basis = In::resident && sI[5] >= 2;   // refused for this call: the basis as it stands
+            const int err = In::resident && sI[5] == 3 ? DLP_ERR_STATE : DLP_ERR_ARG;
             if (tid == 0) {
-                if (out.status) out.status[lp] = DLP_ERR_ARG;
+                if (out.status) out.status[lp] = err;
                 if (out.npivots) out.npivots[lp] = 0;
                 if (out.objective) out.objective[lp] = nan;
             }
@@ -302,13 +355,122 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
             __syncthreads();
         }
     }
+    if constexpr (In::dual) if (sI[0] == 0) {   // (uniform; sI[0] is next written after the pivot loop's first barrier)
+        // The RHS rebuild (dlp.h, dlp_batch_resolve_rhs's rule): the slack columns of the full
+        // layout are B^-1, so row r's new RHS is the fold of Tfull[r][n + l] * b_l over l
+        // ascending, one thread per row (the objective row included: its entry is the new
+        // objective value).  inv[l] says where slack l lives: >= 0 its slot, else -(row + 1) of
+        // the row it is basic in, whose column is that row's unit vector (objective entry +0.0:
+        // a term that cannot change a bit, so it is left out).  inv borrows the entering
+        // column's place, b_l is one uniform load per step.
+        int32_t* inv = (int32_t*)colq;
+        const double* __restrict__ b = in.b + lp * in.sb;
+        for (int s = tid; s < n; s += blockDim.x)
+            if (var[s] >= n) inv[var[s] - n] = s;
+        for (int i = tid; i < m; i += blockDim.x)
+            if (basis[i] >= n) inv[basis[i] - n] = -(i + 1);
+        __syncthreads();
+        for (int r = tid; r <= m; r += blockDim.x) {
+            double acc = 0.0;
+            for (int l = 0; l < m; ++l) {
+                const int iv = inv[l];
+                if (iv >= 0) acc = fold_step(acc, T[r * W + iv], b[l]);
+                else if (iv == -(r + 1)) acc = fold_step(acc, 1.0, b[l]);
+            }
+            T[r * W + n] = acc;
+        }
+        __syncthreads();
+    }
 
     int64_t k = 0;
-    if constexpr (In::resident) {
+    if constexpr (In::resident && !In::dual) {
         // resumed without a new objective: an optimal or unbounded LP does no pivot
         if (sI[3] == DLP_OK || sI[3] == DLP_UNBOUNDED) max_pivots = 0;
     }
-    for (; k < max_pivots; ++k) {
+    int q = -1, sq = -1, p = -1;
+    for (; In::dual || k < max_pivots; ++k) {
+      if constexpr (In::dual) {
+        // ---- d1 leaving row (wave 0): the most negative RHS below -tol_feas, ties -> the smallest
+        // basic VARIABLE; Bland -> the eligible row with the smallest basic variable
+        if (wid == 0) {
+            double rmin = __builtin_inf();
+            int bmin = kNoIndex, imin = -1, bb = kNoIndex, ib = -1;
+            for (int i = lane; i < m; i += 64) {
+                const double v = T[i * W + n];
+                const int bv = basis[i];
+                if (v < -in.tol_feas) {
+                    if (v < rmin || (v == rmin && bv < bmin)) { rmin = v; bmin = bv; imin = i; }
+                    if (bv < bb) { bb = bv; ib = i; }
+                }
+            }
+#pragma unroll
+            for (int sh = 32; sh >= 1; sh >>= 1) {
+                const double orr = __shfl_xor(rmin, sh);
+                const int obm = __shfl_xor(bmin, sh), oim = __shfl_xor(imin, sh);
+                const int obb = __shfl_xor(bb, sh), oib = __shfl_xor(ib, sh);
+                if (orr < rmin || (orr == rmin && obm < bmin)) { rmin = orr; bmin = obm; imin = oim; }
+                if (obb < bb) { bb = obb; ib = oib; }
+            }
+            if (lane == 0) sI[2] = sI[4] ? ib : imin;
+        }
+        __syncthreads();
+        p = sI[2];
+        if (p < 0) {   // primal feasible too: optimal (tested before the budget)
+            if (tid == 0) sI[3] = DLP_OK;
+            break;
+        }
+        if (k >= max_pivots) break;
+        // ---- d2 entering slot (wave 0): min over a = T[p][s] < -tol_piv of max(z_s, 0) / -a,
+        // ties -> the smallest variable; then select + log as the primal's a4
+        if (wid == 0) {
+            double rbest = __builtin_inf(), abest = 0.0;
+            int vbest = kNoIndex, sbest = -1;
+            const double* z = T + m * W;
+            const double* rowp = T + p * W;
+            for (int s = lane; s < n; s += 64) {
+                const double a = rowp[s];
+                if (a < -tol_piv) {
+                    double zz = z[s];
+                    if (!(zz > 0.0)) zz = 0.0;
+                    const double r = zz / (-a);
+                    const int vr = var[s];
+                    if (r < rbest || (r == rbest && vr < vbest)) { rbest = r; vbest = vr; sbest = s; abest = a; }
+                }
+            }
+#pragma unroll
+            for (int sh = 32; sh >= 1; sh >>= 1) {
+                const double orr = __shfl_xor(rbest, sh), oa = __shfl_xor(abest, sh);
+                const int ov = __shfl_xor(vbest, sh), os = __shfl_xor(sbest, sh);
+                if (orr < rbest || (orr == rbest && ov < vbest)) { rbest = orr; vbest = ov; sbest = os; abest = oa; }
+            }
+            if (lane == 0) {
+                sI[1] = sbest;
+                if (sbest >= 0) {
+                    const int leaving = basis[p];
+                    basis[p] = vbest;
+                    var[sbest] = leaving;   // the entering slot now holds the leaving variable
+                    sI[0] = vbest;
+                    sI[4] = (pricing == DLP_PRICING_BLAND) ? 1 : (rbest == 0.0 ? 1 : 0);
+                    sD[0] = abest;
+                    sD[1] = rbest;
+                    if (out.logs && k < out.log_cap) {
+                        dlp_pivot e;
+                        e.q = vbest; e.p = p; e.leaving = leaving; e.pad = 0;
+                        e.ratio = rbest; e.objective = 0.0;
+                        out.logs[lp * out.log_cap + k] = e;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        sq = sI[1];
+        if (sq < 0) {   // no entry of row p can take its RHS up: no x satisfies the row
+            if (tid == 0) sI[3] = DLP_INFEASIBLE;
+            break;
+        }
+        q = sI[0];
+        for (int i = tid; i <= m; i += blockDim.x) colq[i] = T[i * W + sq];
+      } else {
         // ---- a1 pricing (wave 0): lexicographic (z, variable) min + first variable < -tol
         if (wid == 0) {
             double zmin = __builtin_inf();
@@ -342,7 +504,7 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
             }
         }
         __syncthreads();
-        const int q = sI[0], sq = sI[1];
+        q = sI[0], sq = sI[1];
         if (q < 0) {
             if (tid == 0) sI[3] = DLP_OK;
             break;
@@ -397,11 +559,12 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
             }
         }
         __syncthreads();
-        const int p = sI[2];
+        p = sI[2];
         if (p < 0) {
             if (tid == 0) sI[3] = DLP_UNBOUNDED;
             break;
         }
+      }
         // ---- a3 pivot row (IEEE division), then the elimination: work items (slot,
         // row group), R row groups so that the lanes share it evenly; rows 8 at a time,
         // loads first
@@ -447,7 +610,8 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
         if (out.npivots) out.npivots[lp] = k;
         if (out.objective) out.objective[lp] = T[m * W + n];
     }
-    store_state(stt);
+    // (a dual phase the budget stopped is stored as pending: the primal rule must not continue it)
+    store_state(In::dual && stt == DLP_PIVOT_LIMIT ? kDualPending : stt);
     if (out.basis)
         for (int i = tid; i < m; i += blockDim.x) out.basis[lp * m + i] = basis[i];
     // x and y from the tableau as it stands, every index written exactly once (no zero fill):
@@ -682,7 +846,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
     __shared__ int32_t s_p, s_leave, s_bland;
     __shared__ double s_piv;
     __shared__ uint64_t s_zm;   // rows 0..63 of the entering column that are +-0 (the elimination's skip rule)
-    __shared__ int32_t s_bad;   // dense input: some b_i is not >= 0 (resident: 1 rejected at creation, 2 a bad c_k)
+    __shared__ int32_t s_bad;   // dense input: some b_i is not >= 0 (resident: 1 rejected at creation, 2 a bad c_k, 3 a dual phase left it infeasible or pending)
     __shared__ double s_cb[M];  // resident, new objective: cB_i = c[basis[i]] (+0.0 for a slack)
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int N = n + M;
@@ -758,6 +922,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
                 if (__ballot(nf) != 0 && bad == 0) bad = 2;
                 s_cb[lane] = bv < n ? c[bv] : 0.0;   // cB_i, staged once per LP
             }
+            // 3: left infeasible or pending by a dual phase (negative RHS entries: DLP_ERR_STATE)
+            if (bad == 0 && (saved == DLP_INFEASIBLE || saved == kDualPending)) bad = 3;
             if (lane == 0) {
                 s_bad = bad;
                 s_bland = has_c ? (pricing == DLP_PRICING_BLAND ? 1 : 0) : si[N];
@@ -802,9 +968,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
     if constexpr (In::dense || In::resident) {
         if (s_bad) {   // (uniform) DLP_ERR_ARG, no pivots, the slack basis, NaN values
             const double nan = __builtin_nan("");
-            const bool resident_basis = In::resident && s_bad == 2;   // a bad c_k: the basis as it stands
+            const bool resident_basis = In::resident && s_bad >= 2;   // refused for this call: the basis as it stands
+            const int err = In::resident && s_bad == 3 ? DLP_ERR_STATE : DLP_ERR_ARG;
             if (tid == 0) {
-                if (out.status) out.status[lp] = DLP_ERR_ARG;
+                if (out.status) out.status[lp] = err;
                 if (out.npivots) out.npivots[lp] = 0;
                 if (out.objective) out.objective[lp] = nan;
             }
@@ -1091,6 +1258,8 @@ struct dlp_batch {
     dlp_options opt{};
     BatchCtx ctx;
     void *dS = nullptr, *dC = nullptr;   // the state records (dlp::BatchState), host objectives staged
+    void* dRb = nullptr;                 // host right-hand sides staged (allocated by the first such call)
+    void* dBlast = nullptr;              // dlp::RhsIn::last (allocated by the first dlp_batch_resolve_rhs)
     int64_t bytes = 0;
     bool reg = false;
 };
@@ -1179,12 +1348,15 @@ struct BatchJob {
     dlp_batch_out out;
     // a resident batch (dlp_batch_*): its own context instead of the device's cached one; the
     // dense kernels keep the final state in it (creation), or continue from it (resolve, with
-    // the new objectives rc: NULL = resume)
+    // the call's per-LP vector vec: the new objectives, n doubles per LP, NULL = resume)
     dlp_batch* batch;
     bool resolve;
-    const double* rc;
-    int64_t rstride;
-    int rc_device;
+    const double* vec;
+    int64_t vstride;
+    int vec_device;
+    // dlp_batch_resolve_rhs: vec holds the new right-hand sides (m doubles per LP) and the dual
+    // instantiation runs
+    bool rhs;
 };
 
 int batched_run(const dlp_options& o, const BatchJob& job) {
@@ -1270,20 +1442,46 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
         dlp::GenIn gin{(const double*)c->dT, ldg};
         dlp::DenseIn dn{};
         dlp::BatchState bst{bt ? (double*)bt->dS : nullptr};
-        dlp::ResIn rin{bst, nullptr, 0};
+        // the call's per-LP vector on the device (resolve: c_k; resolve_rhs: b_k) and its stride
+        const double* dvec = nullptr;
+        int64_t dstride = 0;
+        if (job.rhs && !bt->dBlast) {
+            // (read only for an LP this call's kernel has marked pending, after writing its b_k)
+            const size_t bL = sizeof(double) * nlp * m;
+            if (hipMalloc(&bt->dBlast, bL) != hipSuccess) {
+                (void)hipGetLastError();
+                bt->dBlast = nullptr;
+                dlp::set_error(who + ": the batch's right-hand sides do not fit in device memory");
+                rc = DLP_ERR_OOM;
+                goto done;
+            }
+            bt->bytes += (int64_t)bL;
+        }
         if (job.resolve) {
-            if (job.rc && !job.rc_device) {   // host objectives: packed into the handle's staging buffer
-                const size_t per = sizeof(double) * n;
-                if (job.rstride == 0 || job.rstride == n)
-                    HIP_BTRY(hipMemcpyAsync(bt->dC, job.rc, per * (job.rstride ? nlp : 1), hipMemcpyHostToDevice, s));
+            if (job.vec && !job.vec_device) {   // a host vector: packed into the handle's staging buffer
+                const int64_t cnt = job.rhs ? m : n;   // (right-hand sides: m per LP, their own buffer)
+                const size_t per = sizeof(double) * cnt;
+                if (job.rhs && !bt->dRb) {
+                    if (hipMalloc(&bt->dRb, per * nlp) != hipSuccess) {
+                        (void)hipGetLastError();
+                        bt->dRb = nullptr;
+                        dlp::set_error(who + ": the staging buffer of b does not fit in device memory");
+                        rc = DLP_ERR_OOM;
+                        goto done;
+                    }
+                    bt->bytes += (int64_t)(per * nlp);
+                }
+                void* const dst = job.rhs ? bt->dRb : bt->dC;
+                if (job.vstride == 0 || job.vstride == cnt)
+                    HIP_BTRY(hipMemcpyAsync(dst, job.vec, per * (job.vstride ? nlp : 1), hipMemcpyHostToDevice, s));
                 else
-                    HIP_BTRY(hipMemcpy2DAsync(bt->dC, per, job.rc, sizeof(double) * job.rstride, per, (size_t)nlp,
+                    HIP_BTRY(hipMemcpy2DAsync(dst, per, job.vec, sizeof(double) * job.vstride, per, (size_t)nlp,
                                               hipMemcpyHostToDevice, s));
-                rin.c = (const double*)bt->dC;
-                rin.sc = job.rstride ? n : 0;
+                dvec = (const double*)dst;
+                dstride = job.vstride ? cnt : 0;
             } else {
-                rin.c = job.rc;
-                rin.sc = job.rstride;
+                dvec = job.vec;
+                dstride = job.vstride;
             }
         } else if (!din) {
             dim3 gg((unsigned)((m + 1 + 3) / 4), (unsigned)nlp);
@@ -1325,7 +1523,9 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
         // kernel, for A/B); otherwise the LDS-resident one
         static const bool force_lds = std::getenv("DLP_BATCH_LDS") && std::atoi(std::getenv("DLP_BATCH_LDS")) == 1;
         const int nw = (int)((n + 63) / 64);
-        const bool reg = !force_lds && m == 64 && nw >= 1 && nw <= 3;
+        // (the dual re-solve has an LDS instantiation only: m = 64 goes through it for that call,
+        // on the same records)
+        const bool reg = !force_lds && m == 64 && nw >= 1 && nw <= 3 && !job.rhs;
         // the kernel of this input kind (its own instantiation, so its own dynamic-LDS attribute),
         // timed alone between e0 and e1
         auto launch = [&](auto in) -> hipError_t {
@@ -1337,15 +1537,17 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
             if (e == hipSuccess) e = hipEventRecord(c->e0, s);
             if (e != hipSuccess) return e;
             if (reg) {
-                if (nw == 1)
-                    dlp::batched_reg_kernel<64, 1, In><<<(unsigned)nlp, 64, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
-                                                                                  o.tol_dj, o.tol_piv, bo);
-                else if (nw == 2)
-                    dlp::batched_reg_kernel<64, 2, In><<<(unsigned)nlp, 128, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
-                                                                                   o.tol_dj, o.tol_piv, bo);
-                else
-                    dlp::batched_reg_kernel<64, 3, In><<<(unsigned)nlp, 192, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
-                                                                                   o.tol_dj, o.tol_piv, bo);
+                if constexpr (!In::dual) {   // (reg is false for the dual source)
+                    if (nw == 1)
+                        dlp::batched_reg_kernel<64, 1, In><<<(unsigned)nlp, 64, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
+                                                                                      o.tol_dj, o.tol_piv, bo);
+                    else if (nw == 2)
+                        dlp::batched_reg_kernel<64, 2, In><<<(unsigned)nlp, 128, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
+                                                                                       o.tol_dj, o.tol_piv, bo);
+                    else
+                        dlp::batched_reg_kernel<64, 3, In><<<(unsigned)nlp, 192, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
+                                                                                       o.tol_dj, o.tol_piv, bo);
+                }
             } else {
                 // 512 lanes per LP when few LPs share a CU (LDS > 40 KB each), else 256
                 const unsigned threads = lds > 40 * 1024 ? 512 : 256;
@@ -1354,13 +1556,15 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
             }
             return hipGetLastError();
         };
-        if (job.resolve)
-            HIP_BTRY(launch(rin));
+        if (job.rhs)
+            HIP_BTRY(launch(dlp::RhsIn{bst, dvec, dstride, o.tol_feas, (double*)bt->dBlast}));
+        else if (job.resolve)
+            HIP_BTRY(launch(dlp::ResIn{bst, dvec, dstride}));
         else if (bt)
             HIP_BTRY(launch(dlp::DenseKeepIn{dn, bst}));
         else
             HIP_BTRY(din ? launch(dn) : launch(gin));
-        if (bt) bt->reg = reg;
+        if (bt && !job.rhs) bt->reg = reg;   // (the kernel of creation and of dlp_batch_resolve)
         HIP_BTRY(hipEventRecord(c->e1, s));
         // read back only what the caller asked for: the packed outputs it wants in one copy
         // (objective | pivot counts | status are contiguous), basis, logs, x and y when requested
@@ -1449,7 +1653,7 @@ void batch_destroy(dlp_batch* b) {
     DeviceGuard guard;
     if (b->opt.device >= 0) (void)hipSetDevice(b->opt.device);
     b->ctx.free_all();   // (drains the stream first)
-    for (void* p : {b->dS, b->dC})
+    for (void* p : {b->dS, b->dC, b->dRb, b->dBlast})
         if (p) (void)hipFree(p);
     (void)hipGetLastError();
     delete b;
@@ -1503,9 +1707,31 @@ extern "C" int dlp_batch_resolve(dlp_batch* batch, const double* c, int64_t stri
     if (out) job.out = *out;
     job.batch = batch;
     job.resolve = true;
-    job.rc = c;
-    job.rstride = stridec;
-    job.rc_device = c_is_device;
+    job.vec = c;
+    job.vstride = stridec;
+    job.vec_device = c_is_device;
+    return batched_run(o, job);
+}
+
+extern "C" int dlp_batch_resolve_rhs(dlp_batch* batch, const double* b, int64_t strideb, int b_is_device,
+                                     int64_t max_pivots, const dlp_batch_out* out) {
+    if (!batch || !b || max_pivots < 0 || (out && out->log_cap < 0) || (strideb != 0 && strideb < batch->m) ||
+        (b_is_device != 0 && b_is_device != 1)) {
+        dlp::set_error("dlp_batch_resolve_rhs: bad arguments");
+        return DLP_ERR_ARG;
+    }
+    dlp_options o = batch->opt;
+    o.max_pivots = max_pivots;
+    BatchJob job{};
+    job.who = "dlp_batch_resolve_rhs";
+    job.nlp = batch->nlp; job.m = batch->m; job.n = batch->n;
+    if (out) job.out = *out;
+    job.batch = batch;
+    job.resolve = true;
+    job.rhs = true;
+    job.vec = b;
+    job.vstride = strideb;
+    job.vec_device = b_is_device;
     return batched_run(o, job);
 }
 

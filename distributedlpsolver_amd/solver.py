@@ -654,6 +654,51 @@ class Batch:
         L.check(L.lib().dlp_batch_resolve(self._handle(), ptr, stride, on_dev, budget, C.byref(out)), "dlp_batch_resolve")
         return result()
 
+    def resolve_rhs(self, b, *, max_pivots: int | None = None, want_x: bool = True, want_y: bool = True,
+                    want_basis: bool = False, log_cap: int = 0) -> BatchResult:
+        """dlp_batch_resolve_rhs: re-solve every LP after new right-hand sides by the dual
+        simplex, from its resident basis, for up to max_pivots dual pivots each (default: the
+        max_pivots of creation).  b: (nlp, m) or (m,) for one shared by every LP, a numpy array
+        or a float64 tensor on the batch's device; any finite value, negative ones included.
+        Per LP: OK, INFEASIBLE, PIVOT_LIMIT (the dual phase is pending: call again), ERR_ARG (a
+        b_k entry that is not finite) or ERR_STATE (the LP is not dual feasible: stopped inside
+        a primal solve, or unbounded); the last two leave the LP as it was."""
+        if b is None:
+            raise ValueError("b is required")
+        if hasattr(b, "data_ptr"):
+            import torch
+            if b.dtype != torch.float64:
+                raise ValueError(f"b must be a float64 tensor, not {b.dtype}")
+            if b.device.type != "cuda" or b.device.index != self.device:
+                raise ValueError(f"b is on {b.device}, the batch lives on device {self.device}")
+            shape = tuple(b.shape)
+        else:
+            b = np.asarray(b)
+            if b.dtype.kind not in "fiu":
+                raise ValueError(f"b must be real-valued (float64), not {b.dtype}")
+            shape = b.shape
+        if shape not in ((self.nlp, self.m), (self.m,)):
+            raise ValueError(f"b must have shape ({self.nlp}, {self.m}) or ({self.m},), not {shape}")
+        budget = self.max_pivots if max_pivots is None else int(max_pivots)
+        if budget < 0:
+            raise ValueError("max_pivots must be >= 0")
+        if log_cap < 0:
+            raise ValueError("log_cap must be >= 0")
+        handle = self._handle()
+        on_dev = 0
+        if hasattr(b, "data_ptr"):
+            b = b.contiguous()
+            torch.cuda.current_stream(self.device).synchronize()   # b is complete before the call
+            ptr, on_dev = b.data_ptr(), 1
+        else:
+            b = np.ascontiguousarray(b, dtype=np.float64)
+            ptr = b.ctypes.data
+        stride = self.m if len(shape) == 2 else 0
+        out, result = _batch_outputs(self.nlp, self.m, self.n, want_x, want_y, want_basis, log_cap)
+        L.check(L.lib().dlp_batch_resolve_rhs(handle, ptr, stride, on_dev, budget, C.byref(out)),
+                "dlp_batch_resolve_rhs")
+        return result()
+
     def read(self, k: int):
         """dlp_batch_read: LP k's resident tableau in the full layout ((m+1) x tableau_ld(m, n),
         objective row last) and its basis."""

@@ -24,6 +24,8 @@
  *   the same loop over all the per-impression          dlp_batch_create_dense once, then per
  *     subproblems  R/global_problem.cpp:270-274         iteration dlp_batch_resolve(new weights):
  *     re-weighted by R/allocation_mw.cpp:271-326       every LP warm from its resident basis
+ *   (no reference: budgets / capacities moved          dlp_batch_resolve_rhs(new b): dual simplex
+ *     between runs, the same subproblems)              from every LP's resident basis
  *   Instance::solution_ (private, no getter)           dlp_result_x / dlp_result_y
  *     R/instance.h:34
  *   "Dual Value" stdout  R/global_problem.cpp:320-322  dlp_result_objective
@@ -342,8 +344,9 @@ int dlp_session_step_update(dlp_session* s);
  * finite; DLP_ERR_UNSUPPORTED (text in dlp_last_error): a general or MPS problem, a session
  * created with nranks > 1 or an RCCL id; DLP_ERR_STATE: a failed session, or a caller-driven step
  * in progress (step_candidate done, step_update not yet).
- * Not covered: changes of b or A (they need a dual simplex), a device-pointer c, multi-rank
- * sessions, general LPs.  (Batches: dlp_batch_resolve applies this rule to every resident LP.) */
+ * Not covered: changes of A, changes of b for a single session (they need a dual simplex;
+ * resident batches have one, dlp_batch_resolve_rhs), a device-pointer c, multi-rank sessions,
+ * general LPs.  (Batches: dlp_batch_resolve applies this rule to every resident LP.) */
 int dlp_session_set_objective(dlp_session* s, const double* c, int64_t n, double* kernel_ms);
 int dlp_session_buffer(dlp_session* s, int which, void** dev_ptr, size_t* bytes);
 /* Synchronous host copies of an exchange buffer (for host-side communicators). */
@@ -591,6 +594,63 @@ int dlp_batch_create_dense(int64_t nlp, int64_t m, int64_t n, const dlp_batch_de
  * device are those of creation. */
 int dlp_batch_resolve(dlp_batch* batch, const double* c, int64_t stridec, int c_is_device,
                       int64_t max_pivots, const dlp_batch_out* out);
+/* Re-solve every resident LP after new right-hand sides, by the dual simplex.
+ * After a primal solve the resident tableau is dual feasible for every b, so the dual simplex
+ * continues from it; it pays when b moves a little (budgets, capacities) and the basis mostly
+ * stays.  LP k's new right-hand side is b_k at b + k*strideb, m doubles (strideb 0 = one b for
+ * all LPs, else >= m; b_is_device 0 host / 1 device pointer on the batch's device, complete when
+ * the call is made).  Any finite value is allowed, negative ones included.  Tolerances, pricing
+ * and device are those of creation.  out as in dlp_batch_resolve: npivots and logs are this
+ * call's pivots; objective, x, y and basis come from the tableau as it stands afterwards.
+ *
+ * RHS rebuild.  In the full layout the slack columns are B^-1.  For every stored row
+ *   r = 0 .. m (the objective row included: its entry is the new objective value):
+ *     acc = +0.0;  for l = 0 .. m-1 ascending: acc = acc + (Tfull[r][n+l] * b_l)
+ *     (the product rounded, then the sum: no fma);  T[r][N] = acc.
+ *   Tfull[.][n+l] is slack l's stored slot when it is nonbasic, the unit vector of its row with
+ *   objective entry +0.0 when it is basic.  (A term whose coefficient is +-0 cannot change a
+ *   bit: acc starts at +0.0, and a sum is -0.0 only if both operands are.)  One ascending fold
+ *   per row: the result depends on nothing but the variable indices.
+ * Dual pivot.  Every nonbasic variable (stored slot) is a candidate.
+ *   Leaving row: row i < m is eligible when T[i][N] < -tol_feas (dlp_options.tol_feas of
+ *     creation, absolute here).  p = argmin T[i][N] over the eligible rows, exact ties to the
+ *     smallest basis[i]; in Bland mode the eligible row with the smallest basis[i].
+ *   Stops: no eligible row -> DLP_OK (dual and primal feasible).  This test comes before the
+ *     budget test: max_pivots == 0 reports DLP_OK on an LP that needs no pivot and
+ *     DLP_PIVOT_LIMIT on one that needs some.
+ *   Entering slot: slots s with a = T[p][s] < -tol_piv; r_s = zc / (-a) by IEEE division, where
+ *     zc = z_s if z_s > 0 else +0.0 (the primal's clamp of its RHS); q = argmin r_s, exact ties
+ *     to the smallest variable index.  No such slot -> DLP_INFEASIBLE.
+ *   Update: exactly the primal one with the negative pivot T[p][q] (division for the pivot row,
+ *     fma elimination, rows with T[i][q] == 0 untouched, the entering slot takes the leaving
+ *     variable's column, var and basis swapped).
+ *   Log entry: q, p, leaving, ratio = r_q, objective after the pivot.
+ *   Bland state: reset at the call (on for DLP_PRICING_BLAND, else off), entered after a pivot
+ *     with r_q == 0 and left after one with r_q > 0.
+ *   The dual phase does not fall through into a primal phase.
+ * Per-LP outcomes, checked in the kernel (host and device b alike) in this order; each leaves
+ *   that LP's resident state bit for bit as it was, and the other LPs run:
+ *   1. rejected at creation: DLP_ERR_ARG, NaN objective / x / y, the slack basis;
+ *   2. a b_k entry that is not finite: DLP_ERR_ARG, NaN values, 0 pivots, the basis as it stands;
+ *   3. not dual feasible, some stored slot has z_s < -tol_dj (an LP stopped inside a primal
+ *      solve, or unbounded): DLP_ERR_STATE, NaN values, 0 pivots, the basis as it stands.
+ * State afterwards: an LP left DLP_INFEASIBLE, or stopped by the budget inside the dual phase
+ *   (reported DLP_PIVOT_LIMIT), has negative RHS entries.  dlp_batch_resolve (with or without c)
+ *   reports DLP_ERR_STATE for it (NaN values, 0 pivots, the basis as it stands, state
+ *   untouched); dlp_batch_resolve_rhs accepts it again: a later b may make it feasible, more
+ *   budget may finish it.  After DLP_OK, dlp_batch_resolve behaves as after any optimal solve.
+ * Continuation: an LP whose dual phase the budget stopped, handed the very b_k of that call
+ *   again (every entry bit for bit; the batch keeps each LP's last accepted b_k), goes on from
+ *   its RHS column and its Bland state as they stand, without a rebuild: budgets of any size
+ *   give the pivots, basis and objective bits of one unbounded call.  (A rebuilt column equals
+ *   the updated one only up to rounding.)  Any other b_k, and every LP that is not pending,
+ *   takes the rebuild and the reset above.
+ * Call-level errors (validated before anything is enqueued, the batch unchanged): DLP_ERR_ARG
+ *   for a NULL batch or b, a stride that is neither 0 nor >= m, b_is_device not 0 / 1, negative
+ *   max_pivots or log_cap.
+ * Not covered: changes of A, c and b in one call, single sessions, general LPs. */
+int dlp_batch_resolve_rhs(dlp_batch* batch, const double* b, int64_t strideb, int b_is_device,
+                          int64_t max_pivots, const dlp_batch_out* out);
 /* LP k's resident tableau in the full layout of dlp_session_tableau ((m+1) x dlp_tableau_ld(m,n),
  * basic columns as exact unit vectors, their objective entries +0.0, padding +0.0) and its
  * basis (m entries).  Either pointer may be NULL. */
