@@ -353,6 +353,22 @@ hipError_t launch_reopt(const Geometry& g, int64_t n, int64_t N, const int32_t* 
                         const double* cblist, int64_t R, const double* c, const int32_t* basic,
                         DevState* st, int pricing, hipStream_t s);
 
+// dlp_dual.hip: the dual simplex of a full-layout, single-rank session after new right-hand sides
+// (DESIGN.md §21).  rhs_rebuild: column N of every stored row folded from the slack block and b
+// (m doubles, device), one ascending unfused fold per row; also sets the state running with the
+// Bland state of the options.  dual_row: the leaving row into st->p / p_local / leaving, or
+// DLP_OK when no row is below -tol_feas.  dual_col: the entering column of row st->p_local and the
+// whole selection (do_select), or DLP_INFEASIBLE.  partials: >= max(dual_row_blocks,
+// dual_col_blocks) entries.  The pivot then continues with launch_gather_q / _prow / _update.
+int dual_row_blocks(const Geometry& g);
+int dual_col_blocks(const Geometry& g);
+hipError_t launch_rhs_rebuild(const Geometry& g, int64_t n, const double* b, DevState* st, int pricing,
+                              hipStream_t s);
+hipError_t launch_dual_row(const Geometry& g, const int32_t* basis, DevState* st, Cand* partials,
+                           double tol_feas, hipStream_t s);
+hipError_t launch_dual_col(const Geometry& g, int32_t* basis, DevState* st, Cand* partials, double tol_piv,
+                           int pricing, dlp_pivot* log, int64_t log_cap, hipStream_t s);
+
 // dlp_batched.hip: free the cached dlp_batched_solve contexts of `device` (-1: all); bytes freed
 size_t batched_release(int device);
 

@@ -187,6 +187,15 @@ struct dlp_session {
     double* ro_c = nullptr;
     int32_t* ro_basic = nullptr;
     hipEvent_t ro_ev[2] = {nullptr, nullptr};
+    // dlp_session_set_rhs, allocated at its first call: b on the device, the
+    // partials of the two dual selections, the rebuild kernel's events.  dual: the session is in
+    // the dual phase that call started (dlp_session_run does dual pivots) until
+    // dlp_session_set_objective starts a primal one; dual_pending(): the RHS may be negative.
+    double* du_b = nullptr;
+    dlp::Cand* du_part = nullptr;
+    hipEvent_t du_ev[2] = {nullptr, nullptr};
+    bool dual = false;
+    bool graph_dual = false;   // the captured window holds dual pivots
 };
 
 extern "C" int flush_pending(dlp_session* s);   // defined with the C entry points
@@ -541,9 +550,11 @@ void free_session(dlp_session* s) {
     void* dev[] = {s->Tb[0] ? s->Tb[0] : s->T, s->Tb[1], s->colq, s->prow_send, s->partials,
                    s->cand_send, s->cand_recv, s->pp, s->basis, s->st, s->log, s->d.C, s->d.Cc,
                    s->d.P, s->d.rhs, s->d.nzc, s->cl_gran, s->band_cnt, s->g.cd.slot_of, s->g.cd.var_of,
-                   s->g.cd.rst, s->ro_rows, s->ro_cb, s->ro_c, s->ro_basic};
+                   s->g.cd.rst, s->ro_rows, s->ro_cb, s->ro_c, s->ro_basic, s->du_b, s->du_part};
     for (void* p : dev) pool_release(s, s->device, p);
     for (hipEvent_t e : s->ro_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : s->du_ev)
         if (e) (void)hipEventDestroy(e);
     if (s->la || s->dslot[1].C) {   // slot 0 aliases s->d
         void* sl[] = {s->dslot[1].C, s->dslot[1].Cc, s->dslot[1].P, s->dslot[1].nzc};
@@ -1473,7 +1484,42 @@ int pivot_phase(dlp_session* s, int phase, int64_t slot, bool last) {
     return s->d.K > 1 ? pivot_defer_phase(s, phase, slot, last) : pivot_eager_phase(s, phase, slot);
 }
 
+// One dual pivot (dlp_session_set_rhs accepted the session: single rank, full
+// layout, eager): leaving row, entering column + selection, then the eager primal's column
+// capture, pivot row and rank-1 update with the negative pivot.  A plain chain of launches, each
+// a no-op once the status is not running.  Timing events as pivot_eager_phase records them (the
+// two selections are the ratio phase, the column capture belongs to the pivot-row phase).
+int enqueue_dual_pivot(dlp_session* s, int64_t slot) {
+    const dlp_options& o = s->opt;
+    hipEvent_t* ev = s->ev_per_pivot ? &s->ev[(size_t)slot * s->ev_per_pivot] : nullptr;
+    const bool all = s->ev_per_pivot == 5;
+    if (all) HIP_TRY(hipEventRecord(ev[0], s->stream));
+    HIP_TRY(dlp::launch_dual_row(s->g, s->basis, s->st, s->du_part, o.tol_feas, s->stream));
+    HIP_TRY(dlp::launch_dual_col(s->g, s->basis, s->st, s->du_part, o.tol_piv, o.pricing, s->log, s->log_cap,
+                                 s->stream));
+    if (all) HIP_TRY(hipEventRecord(ev[1], s->stream));
+    if (all) HIP_TRY(hipEventRecord(ev[2], s->stream));
+    HIP_TRY(dlp::launch_gather_q(s->g, s->st, s->colq, s->stream));
+    CALL_TRY(enqueue_prow(s));
+    if (all) HIP_TRY(hipEventRecord(ev[3], s->stream));
+    if (s->ev_per_pivot == 2) HIP_TRY(hipEventRecord(ev[0], s->stream));
+    CALL_TRY(enqueue_update(s));
+    if (all) HIP_TRY(hipEventRecord(ev[4], s->stream));
+    if (s->ev_per_pivot == 2) HIP_TRY(hipEventRecord(ev[1], s->stream));
+    return DLP_OK;
+}
+
+// The RHS of a session in a dual phase that has not ended DLP_OK may hold negative entries: only
+// dlp_session_set_rhs and dlp_session_run may touch it.
+bool dual_pending(const dlp_session* s) { return s->dual && s->status != DLP_OK; }
+int dual_step_refused(const char* fn) {
+    set_error(std::string(fn) + ": a dual phase is pending or ended infeasible (the right-hand side has "
+              "negative entries): finish it with dlp_session_run or call dlp_session_set_rhs");
+    return DLP_ERR_STATE;
+}
+
 int enqueue_pivot(dlp_session* s, int64_t slot, bool last = true) {
+    if (s->dual) return enqueue_dual_pivot(s, slot);
     for (int ph = 0; ph < 3; ++ph) CALL_TRY(pivot_phase(s, ph, slot, last));
     return DLP_OK;
 }
@@ -1686,7 +1732,7 @@ int poll(dlp_session* s) {
     if (s->host_st->status != DLP_RUNNING && s->host_st->status != dlp::kStatusSkip &&
         s->status == DLP_RUNNING)
         s->status = s->host_st->status;
-    if (s->cluster && s->ev_per_pivot && s->ev_pending > 0) {   // one launch per window
+    if (s->cluster && !s->dual && s->ev_per_pivot && s->ev_pending > 0) {   // one launch per window
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[s->ev_per_pivot - 1]));
         s->timings[DLP_PHASE_UPDATE] += ms;
@@ -1735,7 +1781,7 @@ int poll(dlp_session* s) {
 }
 
 int run_window_graph(dlp_session* s, int64_t chunk) {
-    if (!s->gexec || s->graph_chunk != chunk) {
+    if (!s->gexec || s->graph_chunk != chunk || s->graph_dual != s->dual) {
         if (s->gexec) { (void)hipGraphExecDestroy(s->gexec); s->gexec = nullptr; }
         if (s->graph) { (void)hipGraphDestroy(s->graph); s->graph = nullptr; }
         StageClock clk;
@@ -1751,6 +1797,7 @@ int run_window_graph(dlp_session* s, int64_t chunk) {
         HIP_TRY(hipGraphInstantiate(&s->gexec, s->graph, nullptr, nullptr, 0));
         clk.mark("run: graph instantiate");
         s->graph_chunk = chunk;
+        s->graph_dual = s->dual;
     }
     HIP_TRY(hipGraphLaunch(s->gexec, s->stream));
     return DLP_OK;
@@ -2751,9 +2798,12 @@ int dlp_session_run(dlp_session* s, int64_t max_pivots, int64_t* pivots_done) {
             continue;
         }
         // a small-LP window is one launch that stops by itself at the optimum: poll less
+        // (a dual phase runs the HBM kernels in every session: a small-LP session's tableau is in
+        // s->T between windows)
+        const bool cluster = s->cluster && !s->dual;
         const int64_t chunk = std::min<int64_t>(
-            budget, s->cluster ? std::max<int64_t>(s->opt.check_interval, 1024) : s->opt.check_interval);
-        if (s->cluster) {
+            budget, cluster ? std::max<int64_t>(s->opt.check_interval, 1024) : s->opt.check_interval);
+        if (cluster) {
             CALL_TRY(enqueue_cluster(s, chunk));
         } else if (graph && chunk == s->opt.check_interval) {
             CALL_TRY(run_window_graph(s, chunk));
@@ -2763,6 +2813,12 @@ int dlp_session_run(dlp_session* s, int64_t max_pivots, int64_t* pivots_done) {
         }
         s->launched += chunk;
         budget -= chunk;
+        CALL_TRY(poll(s));
+    }
+    // a dual phase tests "no row is eligible" before any budget: a tableau that
+    // this call's last pivot, or the rebuild alone, made feasible is reported DLP_OK at once
+    if (s->dual && s->status == DLP_RUNNING) {
+        HIP_TRY(dlp::launch_dual_row(s->g, s->basis, s->st, s->du_part, s->opt.tol_feas, s->stream));
         CALL_TRY(poll(s));
     }
     if (pivots_done) *pivots_done = s->npivots - start;
@@ -2819,6 +2875,7 @@ int flush_pending(dlp_session* s) {
 
 int dlp_session_step_candidate(dlp_session* s) {
     if (!s) return DLP_ERR_ARG;
+    if (dual_pending(s)) return dual_step_refused("dlp_session_step_candidate");
     HIP_TRY(hipSetDevice(s->device));
     CALL_TRY(la_disable(s));   // the step API drives single-buffer blocks
     s->step_void = false;
@@ -2843,6 +2900,7 @@ int dlp_session_step_candidate(dlp_session* s) {
 
 int dlp_session_step_select(dlp_session* s) {
     if (!s) return DLP_ERR_ARG;
+    if (dual_pending(s)) return dual_step_refused("dlp_session_step_select");
     HIP_TRY(hipSetDevice(s->device));
     if (s->step_void) return DLP_OK;
     switch (s->step_kind) {
@@ -2857,6 +2915,7 @@ int dlp_session_step_select(dlp_session* s) {
 
 int dlp_session_step_update(dlp_session* s) {
     if (!s) return DLP_ERR_ARG;
+    if (dual_pending(s)) return dual_step_refused("dlp_session_step_update");
     HIP_TRY(hipSetDevice(s->device));
     s->step_open = false;
     if (s->step_void) return DLP_OK;
@@ -2903,6 +2962,11 @@ int dlp_session_set_objective(dlp_session* s, const double* c, int64_t n, double
     if (s->step_open) {
         set_error("dlp_session_set_objective: a caller-driven step is in progress (finish it with "
                   "dlp_session_step_update)");
+        return DLP_ERR_STATE;
+    }
+    if (dual_pending(s)) {
+        set_error("dlp_session_set_objective: a dual phase is pending or ended infeasible (the right-hand "
+                  "side has negative entries): finish it with dlp_session_run or call dlp_session_set_rhs");
         return DLP_ERR_STATE;
     }
     HIP_TRY(hipSetDevice(s->device));
@@ -2958,6 +3022,97 @@ int dlp_session_set_objective(dlp_session* s, const double* c, int64_t n, double
     s->host_st->status = DLP_RUNNING;
     // the pivot budget counts pivots: launches enqueued after the previous optimum did none
     s->launched = s->npivots;
+    s->dual = false;   // a primal phase again
+    return DLP_OK;
+}
+
+// Warm re-solve after new right-hand sides: the resident tableau of an optimal
+// session is dual feasible for every b and its slack columns are B^-1, so a new b needs only a
+// new RHS column (the fold of dlp_dual.hip) and dual pivots from the basis as it stands
+// (dlp_session_run).  Everything is validated before anything is enqueued, so an error leaves the
+// session as it was.
+int dlp_session_set_rhs(dlp_session* s, const double* b, int64_t m, double* kernel_ms) {
+    if (!s || !b) return DLP_ERR_ARG;
+    const int64_t m_user = s->general ? s->prob_dims.m : s->m;
+    if (m != m_user) {
+        set_error("dlp_session_set_rhs: b has " + std::to_string(m) + " entries, the problem " +
+                  std::to_string(m_user) + " rows");
+        return DLP_ERR_ARG;
+    }
+    for (int64_t i = 0; i < m; ++i)
+        if (!std::isfinite(b[i])) {
+            set_error("dlp_session_set_rhs: b[" + std::to_string(i) + "] is not finite");
+            return DLP_ERR_ARG;
+        }
+    if (s->general) {
+        set_error("dlp_session_set_rhs: general / MPS problems are not supported (their right-hand sides "
+                  "live in the standard form's rows and its Phase I)");
+        return DLP_ERR_UNSUPPORTED;
+    }
+    if (s->nranks > 1 || s->exchange) {
+        set_error("dlp_session_set_rhs: single-GPU sessions only (the dual selections would cross the "
+                  "ranks of a row-block session)");
+        return DLP_ERR_UNSUPPORTED;
+    }
+    if (s->d.K > 1 || s->la || s->g.cd.on) {
+        set_error("dlp_session_set_rhs: a deferred session (defer = " + std::to_string(s->d.K) +
+                  ") is not supported: its replay state and RHS cache would have to be re-established "
+                  "after the eager dual pivots; create the session with defer = 1");
+        return DLP_ERR_UNSUPPORTED;
+    }
+    if (s->status < 0) {
+        set_error("dlp_session_set_rhs: the session has failed");
+        return DLP_ERR_STATE;
+    }
+    if (s->step_open) {
+        set_error("dlp_session_set_rhs: a caller-driven step is in progress (finish it with "
+                  "dlp_session_step_update)");
+        return DLP_ERR_STATE;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    // dual feasibility: the objective row and the basis as the device has them (reads only)
+    std::vector<int32_t> basis(s->m);
+    std::vector<double> z(s->N);
+    HIP_TRY(hipMemcpyAsync(basis.data(), s->basis, sizeof(int32_t) * s->m, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(z.data(), s->T + s->rows * s->ld, sizeof(double) * s->N, hipMemcpyDeviceToHost,
+                           s->stream));
+    CALL_TRY(poll(s));   // (synchronises the stream; npivots and status as the device has them)
+    {
+        std::vector<uint8_t> basic(s->N, 0);
+        for (int64_t i = 0; i < s->m; ++i)
+            if (basis[i] >= 0 && basis[i] < s->N) basic[basis[i]] = 1;
+        for (int64_t j = 0; j < s->N; ++j)
+            if (!basic[j] && z[j] < -s->opt.tol_dj) {
+                set_error("dlp_session_set_rhs: the tableau is not dual feasible (z[" + std::to_string(j) +
+                          "] = " + std::to_string(z[j]) + " < -tol_dj: a session stopped inside a primal "
+                          "solve, or an unbounded one); run it to DLP_OK first");
+                return DLP_ERR_STATE;
+            }
+    }
+    // (each on its own: a call that failed half-way through them leaves the rest for the next one)
+    if (!s->du_b)
+        HIP_TRY(pool_alloc(s, s->device, (void**)&s->du_b, sizeof(double) * std::max<int64_t>(s->m, 1)));
+    if (!s->du_part) {
+        const int64_t parts = std::max(dlp::dual_row_blocks(s->g), dlp::dual_col_blocks(s->g));
+        HIP_TRY(pool_alloc(s, s->device, (void**)&s->du_part, sizeof(dlp::Cand) * parts));
+    }
+    for (hipEvent_t& e : s->du_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipMemcpyAsync(s->du_b, b, sizeof(double) * m, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipEventRecord(s->du_ev[0], s->stream));
+    HIP_TRY(dlp::launch_rhs_rebuild(s->g, s->n, s->du_b, s->st, s->opt.pricing, s->stream));
+    HIP_TRY(hipEventRecord(s->du_ev[1], s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (kernel_ms) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, s->du_ev[0], s->du_ev[1]));
+        *kernel_ms = ms;
+    }
+    s->status = DLP_RUNNING;
+    s->host_st->status = DLP_RUNNING;
+    // the pivot budget counts pivots: launches enqueued after the previous optimum did none
+    s->launched = s->npivots;
+    s->dual = true;
     return DLP_OK;
 }
 

@@ -290,6 +290,22 @@ class Session:
                 "dlp_session_set_objective")
         return ms.value
 
+    def set_rhs(self, b) -> float:
+        """Replace the right-hand side by b (m float64 values, any sign) and put the session into
+        a dual phase from its current basis (dlp_session_set_rhs: a warm re-solve; run() then does
+        dual pivots and ends OK or INFEASIBLE).  Eager and small-LP sessions of an optimal tableau.
+        Returns the device time (ms) of the RHS rebuild."""
+        b = np.asarray(b)
+        if b.dtype.kind not in "fiu":
+            raise ValueError(f"b must be real-valued (float64), not {b.dtype}")
+        if b.shape != (self.problem.m,):
+            raise ValueError(f"b must have shape ({self.problem.m},), not {b.shape}")
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        ms = C.c_double()
+        L.check(L.lib().dlp_session_set_rhs(self._h, _dptr(b), b.shape[0], C.byref(ms)),
+                "dlp_session_set_rhs")
+        return ms.value
+
     def status(self) -> tuple[int, int]:
         st, n = C.c_int(), C.c_int64()
         L.check(L.lib().dlp_session_status(self._h, C.byref(st), C.byref(n)), "dlp_session_status")

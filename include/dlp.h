@@ -26,6 +26,8 @@
  *     re-weighted by R/allocation_mw.cpp:271-326       every LP warm from its resident basis
  *   (no reference: budgets / capacities moved          dlp_batch_resolve_rhs(new b): dual simplex
  *     between runs, the same subproblems)              from every LP's resident basis
+ *   (no reference: the same change on the one          dlp_session_set_rhs + dlp_session_run (dual
+ *     global LP, R/global_problem.cpp:257-323)          pivots from the session's resident basis)
  *   Instance::solution_ (private, no getter)           dlp_result_x / dlp_result_y
  *     R/instance.h:34
  *   "Dual Value" stdout  R/global_problem.cpp:320-322  dlp_result_objective
@@ -342,12 +344,66 @@ int dlp_session_step_update(dlp_session* s);
  * Errors, each leaving the session exactly as it was (everything is validated before anything
  * is enqueued): DLP_ERR_ARG: s or c NULL, n differs from the problem's n, a c_j that is not
  * finite; DLP_ERR_UNSUPPORTED (text in dlp_last_error): a general or MPS problem, a session
- * created with nranks > 1 or an RCCL id; DLP_ERR_STATE: a failed session, or a caller-driven step
- * in progress (step_candidate done, step_update not yet).
- * Not covered: changes of A, changes of b for a single session (they need a dual simplex;
- * resident batches have one, dlp_batch_resolve_rhs), a device-pointer c, multi-rank sessions,
- * general LPs.  (Batches: dlp_batch_resolve applies this rule to every resident LP.) */
+ * created with nranks > 1 or an RCCL id; DLP_ERR_STATE: a failed session, a caller-driven step
+ * in progress (step_candidate done, step_update not yet), or a dual phase that is pending or
+ * ended DLP_INFEASIBLE (dlp_session_set_rhs: the RHS has negative entries).
+ * Not covered: changes of A (changes of b: dlp_session_set_rhs below, eager sessions only), a
+ * device-pointer c, multi-rank sessions, general LPs.  (Batches: dlp_batch_resolve applies this
+ * rule to every resident LP.) */
 int dlp_session_set_objective(dlp_session* s, const double* c, int64_t n, double* kernel_ms);
+/* Replace the right-hand side of a live session by b (m doubles, host pointer; any finite value,
+ * negative ones included) and put the session into a dual phase: the resident
+ * tableau of an optimal session is dual feasible for every b, so the dual simplex continues from
+ * its basis; it pays when b moves a little (budgets, capacities) and the basis mostly stays.  The
+ * call rebuilds the RHS column, the objective entry included, and returns DLP_OK with the session
+ * status DLP_RUNNING; *kernel_ms (may be NULL): device time of the rebuild kernel alone.
+ * dlp_session_run then does dual pivots under its usual budget and window rules and ends
+ * DLP_OK (no row is eligible: primal and dual feasible), DLP_INFEASIBLE (no entering column),
+ * DLP_PIVOT_LIMIT or DLP_RUNNING (the life-time limit or the call's budget is spent).
+ *
+ * The rule is dlp_batch_resolve_rhs's (below), on the session's full-layout tableau:
+ *   RHS rebuild: for every stored row r = 0 .. m: acc = +0.0; for l = 0 .. m-1 ascending:
+ *     acc = acc + (T[r][n+l] * b_l), the product rounded, then the sum (no fma); T[r][N] = acc.
+ *     One ascending fold per row, independent of grid and tuning.
+ *   Leaving row: rows with T[i][N] < -tol_feas (absolute; dlp_options.tol_feas of creation); the
+ *     most negative, exact ties to the smallest basis[i]; in Bland mode the eligible row with the
+ *     smallest basis[i].  No eligible row -> DLP_OK; this test comes before the budget test.
+ *   Entering column: columns j < N with a = T[p][j] < -tol_piv; r_j = zc / (-a) by IEEE division,
+ *     zc = z_j if z_j > 0 else +0.0; the smallest, ties to the smallest j.  (A basic column's entry
+ *     in row p is 0 or 1, never below -tol_piv: no mask is needed.)  None -> DLP_INFEASIBLE.
+ *   Update: the eager update of the pivot rule above, unchanged, with the negative pivot.
+ *   Log entry: q, p, leaving, ratio = r_q, objective after the pivot; appended to the session's log,
+ *     npivots goes on counting (options.max_pivots counts pivots over the session's life).
+ *   Bland state: reset at the call (on for DLP_PRICING_BLAND, else off), entered after a pivot
+ *     with r_q == 0 and left after one with r_q > 0.
+ *   The dual phase never falls through into a primal phase.
+ *
+ * Sessions: single-GPU sessions of dense, random and ad-allocation problems whose tableau is the
+ * full layout in HBM between launches: the eager path (defer = 1) and the one-launch small-LP path
+ * (the dual phase runs the HBM kernels on its tableau; a later primal run goes back to the one
+ * launch).  The call is allowed at any time between runs.
+ *
+ * Errors, each leaving the session bit for bit as it was (everything is validated before anything
+ * is enqueued), checked in this order:
+ *   1. DLP_ERR_ARG: s or b NULL, m differs from the problem's m, a b_i that is not finite;
+ *   2. DLP_ERR_UNSUPPORTED (text in dlp_last_error): a general or MPS problem; a session created
+ *      with nranks > 1 or an RCCL id; a deferred session (defer > 1, full or condensed, with or
+ *      without lookahead): create the session with defer = 1;
+ *   3. DLP_ERR_STATE: a failed session; a caller-driven step in progress; a tableau that is not
+ *      dual feasible, some nonbasic z_j < -tol_dj (a session stopped inside a primal solve, or an
+ *      unbounded one).
+ * State around the dual phase: while it is pending (budget spent) or has ended DLP_INFEASIBLE the
+ *   RHS has negative entries; dlp_session_set_rhs is accepted again (the slack columns are still
+ *   B^-1 and a new b may be feasible), dlp_session_set_objective and dlp_session_step_* return
+ *   DLP_ERR_STATE.  After DLP_OK the session is an ordinary optimal session (dlp_session_run
+ *   returns DLP_OK with 0 pivots; set_objective and set_rhs work).  dlp_session_run continues from
+ *   the tableau as it stands and folds nothing again, so budgets of any size give the pivots of one
+ *   unbounded call.  dlp_session_result reads x, y and the basis from the tableau as it stands, for
+ *   every status.  A negative pivot leaves -0 where a +0 stood in the basic columns of the pivot row;
+ *   no comparison of the rule sees the sign of a zero.
+ * Not covered: deferred sessions (their replay state and RHS cache would have to be re-established
+ * after the eager dual pivots), changes of A, a device-pointer b, multi-rank sessions, general LPs. */
+int dlp_session_set_rhs(dlp_session* s, const double* b, int64_t m, double* kernel_ms);
 int dlp_session_buffer(dlp_session* s, int which, void** dev_ptr, size_t* bytes);
 /* Synchronous host copies of an exchange buffer (for host-side communicators). */
 int dlp_session_read_buffer(dlp_session* s, int which, void* host, size_t bytes);
@@ -648,7 +704,9 @@ int dlp_batch_resolve(dlp_batch* batch, const double* c, int64_t stridec, int c_
  * Call-level errors (validated before anything is enqueued, the batch unchanged): DLP_ERR_ARG
  *   for a NULL batch or b, a stride that is neither 0 nor >= m, b_is_device not 0 / 1, negative
  *   max_pivots or log_cap.
- * Not covered: changes of A, c and b in one call, single sessions, general LPs. */
+ * Not covered: changes of A, c and b in one call, general LPs.  (Single sessions:
+ * dlp_session_set_rhs applies this rule to an eager session's tableau; deferred sessions remain
+ * the gap.) */
 int dlp_batch_resolve_rhs(dlp_batch* batch, const double* b, int64_t strideb, int b_is_device,
                           int64_t max_pivots, const dlp_batch_out* out);
 /* LP k's resident tableau in the full layout of dlp_session_tableau ((m+1) x dlp_tableau_ld(m,n),
