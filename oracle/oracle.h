@@ -75,6 +75,19 @@ int oracle_solve_general(int64_t m, int64_t n, const double* A, const double* rl
                          int32_t* basis, int64_t basis_cap, oracle_pivot* log, int64_t log_cap,
                          int64_t* npivots, int64_t* phase1, int* status);
 
+/* The dual rule of include/dlp.h (dlp_batch_resolve_rhs, dlp_session_set_rhs) on a full-layout
+ * tableau T, (m+1) x ld, objective row last, as dlp_session_tableau and dlp_batch_read return it;
+ * T and basis are updated in place (oracle_dual.inc).  rebuild != 0: fold b into the RHS column
+ * and reset the Bland state from opt->pricing; rebuild == 0: continue from the column as it
+ * stands with the Bland state *bland_io (the continuation of a pending dual phase).  Does up to
+ * opt->max_pivots dual pivots; *status is DLP_OK, DLP_INFEASIBLE or DLP_PIVOT_LIMIT (budget
+ * spent), *bland_io the Bland state afterwards, log the first log_cap pivots.  Returns 0, or the
+ * refusal's code with T and basis untouched: DLP_ERR_ARG (-1) for a b_l that is not finite,
+ * DLP_ERR_STATE (-6) for a nonbasic z_j < -opt->tol_dj. */
+int oracle_resolve_rhs(int64_t m, int64_t n, int64_t ld, double* T, int32_t* basis, const double* b,
+                       const oracle_opts* opt, double tol_feas, int rebuild, int* bland_io,
+                       oracle_pivot* log, int64_t log_cap, int64_t* npivots, int* status);
+
 /* Row-slice engine (one simulated rank) for multi-rank protocol tests. */
 typedef struct oracle_slice oracle_slice;
 int  oracle_slice_create(int64_t m, int64_t n, const double* A, const double* b, const double* c,

@@ -149,6 +149,47 @@ def solve_dense(A, b, c, pricing=0, tol_dj=1e-9, tol_piv=1e-9, max_pivots=1_000_
                     pivot_log=log[:min(npiv.value, cap)], num_pivots=npiv.value)
 
 
+def resolve_rhs(T, basis, n, b, max_pivots=10 ** 6, pricing=0, tol_dj=1e-9, tol_piv=1e-9, tol_feas=1e-9,
+                continued=None):
+    """oracle_resolve_rhs (oracle/oracle_dual.inc): the dual rule of include/dlp.h on one
+    full-layout tableau.  The arguments and the returned dict are tests/rhs_ref.py's
+    resolve_rhs's (status, done, objective, x, y, basis, log, T, bland), so a test can swap one
+    for the other; (T, basis) are not modified."""
+    L = lib()
+    if not getattr(L, "_dual_bound", False):
+        L.oracle_resolve_rhs.argtypes = [C.c_int64, C.c_int64, C.c_int64, _D, _I32, _D, C.POINTER(Opts),
+                                         C.c_double, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_int64,
+                                         _I64, C.POINTER(C.c_int)]
+        L._dual_bound = True
+    T = np.array(T, dtype=np.float64, order="C")
+    basis = np.array(basis, dtype=np.int32)
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    m = len(basis)
+    N = n + m
+    assert T.shape[0] == m + 1 and T.shape[1] >= N + 1 and b.shape == (m,)
+    o = Opts(pricing, tol_dj, tol_piv, max_pivots, 1)
+    cap = int(min(max_pivots, 1 << 16))
+    log = np.zeros(cap, PIVOT_DTYPE)
+    npiv, st = C.c_int64(), C.c_int()
+    bland = C.c_int(1 if continued else 0)
+    rc = L.oracle_resolve_rhs(m, n, T.shape[1], _d(T), basis.ctypes.data_as(_I32), _d(b), C.byref(o),
+                              tol_feas, 1 if continued is None else 0, C.byref(bland), log.ctypes.data,
+                              cap, C.byref(npiv), C.byref(st))
+    if rc != 0:
+        assert rc == st.value and rc in (-1, -6), (rc, st.value)
+        return dict(status=rc, done=0, objective=float("nan"), x=np.full(n, np.nan),
+                    y=np.full(m, np.nan), basis=basis, log=np.zeros(0, PIVOT_DTYPE), T=T)
+    assert npiv.value <= cap, "pivot log capacity"
+    rhs = T[:, N]
+    x = np.zeros(n)
+    rows = np.nonzero(basis < n)[0]
+    x[basis[rows]] = rhs[rows]
+    y = T[m, n:N].copy()
+    y[basis[basis >= n] - n] = 0.0
+    return dict(status=st.value, done=int(npiv.value), objective=rhs[m], x=x, y=y, basis=basis,
+                log=log[:npiv.value].copy(), T=T, bland=bool(bland.value))
+
+
 class OracleEngine:
     """A simulated rank (oracle row slice) with the rowblock engine interface."""
 

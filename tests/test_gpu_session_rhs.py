@@ -388,9 +388,13 @@ def test_random_and_adalloc_problems():
     with dlp.Session(dlp.Problem.adalloc(100, 100, 1, 0.1, 0.25), small_lp=1) as s:
         assert s.run(BIG)[0] == L.OK
         np0 = s.status()[1]
+        T0, basis0 = s.tableau(), s.result().basis
         s.set_rhs(bn)
         st, done = s.run(BIG)
         res = s.result()
+        # the full bar (m = 200: rhs_ref.py is too slow here; the C++ dual oracle is pinned to it
+        # bit for bit by tests/test_oracle_dual.py)
+        _bar("adalloc 100x100", s, st, np0, O.resolve_rhs(T0, basis0, M.shape[1], bn))
     print(f"adalloc 100x100: {np0} cold + {done} dual pivots (oracle cold on the new budgets: {ref.num_pivots})")
     assert st == ref.status == L.OK and res.status == L.OK
     assert _close(res.objective, ref.objective)
