@@ -1952,8 +1952,13 @@ __global__ __launch_bounds__(256) void pass_r_kernel(double* __restrict__ T, int
 // then each step's pivot row raised to the step index (LDS atomic max: the last step that
 // pivoted on the row wins; steps >= 0 exceed every class code).  One load per thread
 // instead of a scan of the step table per row.  The caller syncs.
+// densepiv (form 23): a pivot row whose every coefficient is non-zero (nzc == kb, so every step
+// after its pivot step touches it) gets class kDensePiv + step: its group may stay on the DPP
+// chain (pass_q_kernel).  Only the step that won the row marks it, so the marks do not race.
+constexpr int kDensePiv = 64;
 __device__ inline void classify_band(int32_t* cls, const BlockDesc* __restrict__ bd,
-                                     const int32_t* __restrict__ nzc, int64_t i0, int nr, int kb) {
+                                     const int32_t* __restrict__ nzc, int64_t i0, int nr, int kb,
+                                     bool densepiv = false) {
     for (int r = threadIdx.x; r < nr; r += blockDim.x) {
         const int nz = nzc[i0 + r];
         // (an empty block, out of place, is a copy: C and nzc are the previous block's)
@@ -1963,6 +1968,12 @@ __device__ inline void classify_band(int32_t* cls, const BlockDesc* __restrict__
     for (int l = threadIdx.x; l < kb; l += blockDim.x) {
         const int64_t r = (int64_t)bd->pl[l] - i0;
         if (bd->pl[l] >= 0 && r >= 0 && r < nr) atomicMax(&cls[r], l);
+    }
+    if (!densepiv) return;
+    __syncthreads();
+    for (int l = threadIdx.x; l < kb; l += blockDim.x) {
+        const int64_t r = (int64_t)bd->pl[l] - i0;
+        if (bd->pl[l] >= 0 && r >= 0 && r < nr && cls[r] == l && nzc[i0 + r] == kb) cls[r] = kDensePiv + l;
     }
 }
 
@@ -2156,7 +2167,8 @@ __global__ __launch_bounds__(256) void pass_d_kernel(const double* __restrict__ 
 // vmcnt(0) before the next LDS read, draining the ring: cdna_hip_programming.md, glds);
 // the kernel waits with its own counted vmcnt, which relies on every group issuing exactly
 // U DMAs and U stores (rows with nothing to store aim a store out of range).  Groups whose
-// U rows are all dense run the chains from LDS; any other group replays row by row
+// U rows are all dense, or dense pivot rows (recomputed after the chain: redo_pivot_row),
+// run the chains from LDS; any other group replays row by row
 // (replay_row: T and the coefficients from the slot, P from the registers).  Lab:
 // 7.3-7.5 ms per C3 pass against form 21's 8.2-8.5 (tools/passlab.hip f4r, bit-exact).
 // newer than group g's U DMAs: U per prologue group still to come and 2 U (U stores + U
@@ -2190,19 +2202,57 @@ __device__ __forceinline__ void ring_half(double (&t)[U], const double (&c)[U][2
     (ring_step<U, L0 + I>(t, c, pr), ...);
 }
 
+// A dense pivot row (classify_band, kDensePiv) of a group that ran the chain: its value again,
+// as replay_row computes it: t = P[cl], then the DPP steps l > cl only, the unrolled sequence
+// entered by a uniform test per step (cl in a scalar).  cr: the row's 64 coefficients in the
+// ring slot; each half's registers are written by its LDS load alone.
+template <int L>
+__device__ __forceinline__ void redo_step(double& t, const double (&c)[2], const double (&pr)[64], int cl) {
+    constexpr int e = L & 1, n = (L & 31) >> 1;
+    if (L == cl)
+        t = pr[L];
+    else if (L > cl)
+        fmac_bc<n>(t, c[e], pr[L]);
+}
+template <int L0, int... I>
+__device__ __forceinline__ void redo_half(double& t, const double (&c)[2], const double (&pr)[64], int cl,
+                                          std::integer_sequence<int, I...>) {
+    (redo_step<L0 + I>(t, c, pr, cl), ...);
+}
+__device__ __forceinline__ double redo_pivot_row(const double* cr, int cl, const double (&pr)[64]) {
+    // the lane id, made here: a rare path must not hold an address register across the chain
+    // (the kernel sits at its 168 VGPRs)
+    int lane;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+    double t = 0.0;
+    if (cl < 32) {
+        const d2 v = *(const d2*)(cr + 2 * (lane & 15));
+        const double c0[2] = {v.x, v.y};
+        redo_half<0>(t, c0, pr, cl, std::make_integer_sequence<int, 32>{});
+    }
+    const d2 v = *(const d2*)(cr + 32 + 2 * (lane & 15));
+    const double c1[2] = {v.x, v.y};
+    redo_half<32>(t, c1, pr, cl, std::make_integer_sequence<int, 32>{});
+    return t;
+}
+
 // PUB: band publication as form 21's (pass_d_kernel)
+// pivg: groups of dense and dense pivot rows run the chain too (DLP_PASS_PIVG, default 1)
+// (three waves per SIMD, 168 VGPRs, as before the pivot-row recompute was added)
 template <bool NT, int U, int D, bool PUB = false>
-__global__ __launch_bounds__(256) void pass_q_kernel(const double* __restrict__ T, double* __restrict__ Tout,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void pass_q_kernel(
+                                                     const double* __restrict__ T, double* __restrict__ Tout,
                                                      int64_t ld, int64_t rows, int64_t width,
                                                      const BlockDesc* __restrict__ bd,
                                                      const double* __restrict__ C, int64_t ldc,
                                                      const double* __restrict__ P,
                                                      const int32_t* __restrict__ nzc, int rb,
-                                                     uint32_t* bcnt = nullptr) {
+                                                     uint32_t* bcnt = nullptr, int pivg = 0) {
     constexpr int K = 64, SLOT = 128 * U;   // doubles per ring slot
     constexpr int kSt = (NT ? 2 : 0) | (PUB ? kAuxSc1 : 0);   // store policy
     static_assert(U % 2 == 0, "one DMA carries two rows");
-    __shared__ int32_t cls[1024];
+    __shared__ __attribute__((aligned(16))) int32_t cls[1024];
+    typedef int32_t clsv __attribute__((ext_vector_type(U)));
     extern __shared__ double ring[];   // [4 waves][D slots][SLOT]
     const int kb = bd->blk;
     const bool outplace = Tout != T;
@@ -2218,7 +2268,7 @@ __global__ __launch_bounds__(256) void pass_q_kernel(const double* __restrict__ 
     const int64_t i0 = (int64_t)blockIdx.y * rb;
     const int64_t iend = (i0 + rb < rows) ? i0 + rb : rows;
     const int nr = (int)(iend - i0);
-    classify_band(cls, bd, nzc, i0, nr, kb);
+    classify_band(cls, bd, nzc, i0, nr, kb, pivg != 0);
     __syncthreads();
     // the P loads complete here, before the ring starts (else hipcc waits for them, and
     // with them for everything, at the top of every group)
@@ -2267,9 +2317,15 @@ __global__ __launch_bounds__(256) void pass_q_kernel(const double* __restrict__ 
         vmwait_group<D, U>(g);
         const double* sl = wbase + s * SLOT;
         const int r0 = g * U;
-        bool dense = r0 + U <= nr;
+        // the group's U classes in one LDS read (a short last group is never dense; rb <= 1024)
+        const clsv cv = *(const clsv*)(cls + r0);
+        bool dense = r0 + U <= nr, anyp = false;
 #pragma unroll
-        for (int u = 0; u < U; ++u) dense = dense && cls[r0 + u < nr ? r0 + u : 0] == kDense;
+        for (int u = 0; u < U; ++u) {
+            const int cu = __builtin_amdgcn_readfirstlane(cv[u]);
+            dense = dense && (cu == kDense || cu >= kDensePiv);
+            anyp = anyp || cu >= kDensePiv;
+        }
         if (dense) {   // (uniform)
             double t[U];
 #pragma unroll
@@ -2287,13 +2343,24 @@ __global__ __launch_bounds__(256) void pass_q_kernel(const double* __restrict__ 
             ring_half<U, 0>(t, c, pr, std::make_integer_sequence<int, 32>{});
             loadc(1);
             ring_half<U, 32>(t, c, pr, std::make_integer_sequence<int, 32>{});
+            if (anyp) {   // (uniform; rare: at most kb rows of the whole tableau)
+#pragma nounroll
+                for (int u = 0; u < U; ++u) {
+                    const int cl = __builtin_amdgcn_readfirstlane(cls[r0 + u]) - kDensePiv;
+                    if (cl < 0) continue;
+                    const double tp = redo_pivot_row(sl + U * 64 + u * 64, cl, pr);
+#pragma unroll
+                    for (int k = 0; k < U; ++k) t[k] = k == u ? tp : t[k];
+                }
+            }
 #pragma unroll
             for (int u = 0; u < U; ++u) store(t[u], r0 + u, true);
         } else {
             // generic replay, row by row (form 21's); exactly U stores for the counted waits
             for (int u = 0; u < U; ++u) {
                 const int r = r0 + u;
-                const int cl = r < nr ? cls[r] : kUntouched;
+                int cl = r < nr ? cls[r] : kUntouched;
+                if (cl >= kDensePiv) cl -= kDensePiv;
                 double t = sl[u * 64 + lane];
                 if (cl == kUntouched) {
                     store(t, r, outplace && r < nr);
@@ -2939,6 +3006,8 @@ static hipError_t pass(const Geometry& g, const Defer& d, DevState* st, int rb, 
             // 4.519-4.523 ms, 13,951-13,956 vs 13,753-13,755 pivots/s; c3r2 equal; c3r4's pass 2%
             // slower with U = 4); DLP_Q_U = 2 / 4 overrides
             static const int qu_env = std::getenv("DLP_Q_U") ? std::atoi(std::getenv("DLP_Q_U")) : 0;
+            // groups holding dense pivot rows stay on the DPP chain (DLP_PASS_PIVG=0: the row-by-row replay)
+            static const int pivg = std::getenv("DLP_PASS_PIVG") ? std::atoi(std::getenv("DLP_PASS_PIVG")) : 1;
             const int qu = qu_env == 2 || qu_env == 4 ? qu_env : (g.rows >= 16384 ? 4 : 2);
             constexpr int U = 2;
             const int D = qd == 2 || qd == 3 || qd == 6 || qd == 8 ? qd : 4;
@@ -2951,17 +3020,17 @@ static hipError_t pass(const Geometry& g, const Defer& d, DevState* st, int rb, 
                     if (D4 == 3) {
                         if (bcnt)
                             pass_q_kernel<NT, 4, 3, true><<<grid4, 256, dyn4, s>>>(g.T, To, g.ld, g.rows, g.width, bd,
-                                                                                d.C, d.ldc, d.P, d.nzc, rb, bcnt);
+                                                                                d.C, d.ldc, d.P, d.nzc, rb, bcnt, pivg);
                         else
                             pass_q_kernel<NT, 4, 3><<<grid4, 256, dyn4, s>>>(g.T, To, g.ld, g.rows, g.width, bd, d.C,
-                                                                          d.ldc, d.P, d.nzc, rb);
+                                                                          d.ldc, d.P, d.nzc, rb, nullptr, pivg);
                     } else {
                         if (bcnt)
                             pass_q_kernel<NT, 4, 2, true><<<grid4, 256, dyn4, s>>>(g.T, To, g.ld, g.rows, g.width, bd,
-                                                                                d.C, d.ldc, d.P, d.nzc, rb, bcnt);
+                                                                                d.C, d.ldc, d.P, d.nzc, rb, bcnt, pivg);
                         else
                             pass_q_kernel<NT, 4, 2><<<grid4, 256, dyn4, s>>>(g.T, To, g.ld, g.rows, g.width, bd, d.C,
-                                                                          d.ldc, d.P, d.nzc, rb);
+                                                                          d.ldc, d.P, d.nzc, rb, nullptr, pivg);
                     }
                 }
                 if (seal < 0) blk_reset_kernel<<<1, 64, 0, s>>>(st);
@@ -2974,10 +3043,10 @@ static hipError_t pass(const Geometry& g, const Defer& d, DevState* st, int rb, 
     do {                                                                                                   \
         if (bcnt)                                                                                          \
             pass_q_kernel<NT, U, DD, true><<<grid, 256, dyn, s>>>(g.T, To, g.ld, g.rows, g.width, bd, d.C, \
-                                                                  d.ldc, d.P, d.nzc, rb, bcnt);           \
+                                                                  d.ldc, d.P, d.nzc, rb, bcnt, pivg);     \
         else                                                                                               \
             pass_q_kernel<NT, U, DD><<<grid, 256, dyn, s>>>(g.T, To, g.ld, g.rows, g.width, bd, d.C, d.ldc, \
-                                                           d.P, d.nzc, rb);                                \
+                                                           d.P, d.nzc, rb, nullptr, pivg);                 \
     } while (0)
             if (g.rows > 0) {
                 if (D == 2)
