@@ -84,6 +84,14 @@ __device__ inline void stv(double* p, d2 v) {
 __device__ __forceinline__ void glds16(const void* g, uint32_t m0) {
     asm volatile("s_waitcnt lgkmcnt(0)\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "{m0}"(m0) : "memory");
 }
+// The same DMA in the scalar-base form: lane x reads 16 B at base + voff (voff: unsigned 32-bit bytes),
+// the wave-uniform base in an SGPR pair, so a stream that only advances by a uniform stride needs no
+// per-lane address arithmetic.  The s_nop covers a base that an SALU add has just written (the
+// compiler pads nothing inside the statement).
+__device__ __forceinline__ void glds16s(uint32_t voff, const void* base, uint32_t m0) {
+    asm volatile("s_nop 4\n\ts_waitcnt lgkmcnt(0)\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "{m0}"(m0)
+                 : "memory");
+}
 template <int N>
 __device__ __forceinline__ void vmwait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ uint32_t lds_addr(const void* p) {
@@ -2238,8 +2246,9 @@ __device__ __forceinline__ double redo_pivot_row(const double* cr, int cl, const
 
 // PUB: band publication as form 21's (pass_d_kernel)
 // pivg: groups of dense and dense pivot rows run the chain too (DLP_PASS_PIVG, default 1)
-// (three waves per SIMD, 168 VGPRs, as before the pivot-row recompute was added)
-template <bool NT, int U, int D, bool PUB = false>
+// SA: the LDS-DMAs in the scalar-base form (DLP_PASS_SADDR, default 1)
+// (three waves per SIMD, at most 168 VGPRs, as before the pivot-row recompute was added)
+template <bool NT, int U, int D, bool SA = false, bool PUB = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void pass_q_kernel(
                                                      const double* __restrict__ T, double* __restrict__ Tout,
                                                      int64_t ld, int64_t rows, int64_t width,
@@ -2280,25 +2289,68 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void p
     // row's 64 coefficients
     const int64_t wc = (int64_t)blockIdx.x * 256 + w * 64 + 2 * (lane & 31);
     const int64_t wcc = wc < ld - 1 ? wc : ld - 2;
-    const double* tsrc = T + i0 * ld + wcc;
-    const double* csrc = C + i0 * ldc + 2 * (lane & 31);
     double* wbase = ring + (size_t)w * D * SLOT;
     const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)wbase;
+    // SA: every DMA in the scalar-base form (glds16s).  The base is the DMA's first row, wave-uniform;
+    // the lane's byte offset is fixed for the band: its row of the pair and its clamped column
+    // (tvoff; ld * 8 + wcc * 8 < 2^32 since rb * ld * 8 < 2^31), its 16 B of the pair's 128
+    // coefficients (cvoff).  Steady state: the refilled group lies wholly inside the band, its bases
+    // run ahead by scalar adds (tb, cb: U rows on per group) and no VALU instruction belongs to a
+    // DMA.  Elsewhere (the prologue, the last D refills, a short last group) the row clamp of the
+    // per-lane form is taken on the base, and on a pair whose second row is past the band both
+    // halves read the band's last row: the same source bytes as the per-lane form's.
+    uint32_t tvoff = 0, cvoff = 0;
+    const double *tsrc = nullptr, *csrc = nullptr;
+    if constexpr (SA) {
+        tvoff = (uint32_t)(lane >> 5) * (uint32_t)(ld * 8) + (uint32_t)(wcc * 8);
+        cvoff = 16u * lane;
+    } else {
+        tsrc = T + i0 * ld + wcc;
+        csrc = C + i0 * ldc + 2 * (lane & 31);
+    }
     auto dma = [&](int g, int s) {
         const int gg = g < ng ? g : ng - 1;
 #pragma unroll
         for (int k = 0; k < U / 2; ++k) {
-            int r = gg * U + 2 * k + (lane >> 5);
-            r = r < nr ? r : nr - 1;
-            glds16(tsrc + (int64_t)r * ld, __builtin_amdgcn_readfirstlane(lbase + s * SLOT * 8 + k * 1024));
+            const uint32_t m0 = __builtin_amdgcn_readfirstlane(lbase + s * SLOT * 8 + k * 1024);
+            if constexpr (SA) {
+                const int rk = gg * U + 2 * k;
+                const bool pair = rk + 1 < nr;   // (uniform)
+                const uint32_t up = lane >> 5 ? (uint32_t)(ld * 8) : 0u;
+                glds16s(pair ? tvoff : tvoff - up, T + (i0 + (rk < nr ? rk : nr - 1)) * ld, m0);
+            } else {
+                int r = gg * U + 2 * k + (lane >> 5);
+                r = r < nr ? r : nr - 1;
+                glds16(tsrc + (int64_t)r * ld, m0);
+            }
         }
 #pragma unroll
         for (int k = 0; k < U / 2; ++k) {
-            int r = gg * U + 2 * k + (lane >> 5);
-            r = r < nr ? r : nr - 1;
-            glds16(csrc + (int64_t)r * ldc,
-                   __builtin_amdgcn_readfirstlane(lbase + s * SLOT * 8 + U * 512 + k * 1024));
+            const uint32_t m0 = __builtin_amdgcn_readfirstlane(lbase + s * SLOT * 8 + U * 512 + k * 1024);
+            if constexpr (SA) {
+                const int rk = gg * U + 2 * k;
+                const bool pair = rk + 1 < nr;
+                glds16s(pair ? cvoff : cvoff & 511u, C + (i0 + (rk < nr ? rk : nr - 1)) * ldc, m0);
+            } else {
+                int r = gg * U + 2 * k + (lane >> 5);
+                r = r < nr ? r : nr - 1;
+                glds16(csrc + (int64_t)r * ldc, m0);
+            }
         }
+    };
+    const int ngs = SA ? nr / U : 0;   // refills of groups [D, ngs) are in the steady state
+    const int64_t tstep = (int64_t)U * ld * 8, cstep = (int64_t)U * ldc * 8;
+    const char* tb = (const char*)(T + i0 * ld) + D * tstep;   // group g + D's first row
+    const char* cb = (const char*)(C + i0 * ldc) + D * cstep;
+    auto dma_s = [&](int s) {
+#pragma unroll
+        for (int k = 0; k < U / 2; ++k)
+            glds16s(tvoff, tb + (int64_t)2 * k * ld * 8,
+                    __builtin_amdgcn_readfirstlane(lbase + s * SLOT * 8 + k * 1024));
+#pragma unroll
+        for (int k = 0; k < U / 2; ++k)
+            glds16s(cvoff, cb + (int64_t)2 * k * ldc * 8,
+                    __builtin_amdgcn_readfirstlane(lbase + s * SLOT * 8 + U * 512 + k * 1024));
     };
     // band descriptor (the caller keeps rb * ld * 8 < 2^31): rows at soffset r * ld8; stores
     // of lanes past the width, and of rows with nothing to store, go out of range (dropped)
@@ -2371,7 +2423,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void p
                 store(t, r, true);
             }
         }
-        dma(g + D, s);
+        if (SA && g + D < ngs) {   // (uniform)
+            dma_s(s);
+        } else {
+            dma(g + D, s);
+        }
+        if constexpr (SA) {
+            tb += tstep;
+            cb += cstep;
+        }
         s = s + 1 == D ? 0 : s + 1;
     }
     if constexpr (PUB) {
@@ -2611,8 +2671,19 @@ __global__ __launch_bounds__(256) void drop_failed_step_kernel(const DevState* _
 // replayed by the next block's selections); the next block starts empty.
 // (bcnt: the slot's band counts restart at 0 for the pass about to be launched, whose
 // output the next block's selections poll; the slot's previous pass has finished.)
-__global__ __launch_bounds__(64) void seal_kernel(DevState* st, int slot, uint32_t* bcnt, int64_t nb) {
+// A block that ended on a failed step (drop_failed_step_kernel's case: DLP_UNBOUNDED, rare and
+// terminal) is cleaned here, behind the selection that failed and before the block's pass: column
+// kb of C back to +0 and out of the counts, the 64 lanes over the rows and the objective row.
+__global__ __launch_bounds__(64) void seal_kernel(DevState* st, int slot, uint32_t* bcnt, int64_t nb,
+                                                  double* __restrict__ C, int64_t ldc,
+                                                  int32_t* __restrict__ nzc, int64_t rows) {
     const int kb = st->blk;
+    if (C && nzc && st->status == DLP_UNBOUNDED && kb >= 0 && kb < ldc)
+        for (int64_t i = threadIdx.x; i <= rows; i += 64) {
+            const double a = C[i * ldc + kb];
+            if (i < rows && a != 0.0) nzc[i] = nzc[i] - 1;
+            C[i * ldc + kb] = 0.0;
+        }
     for (int l = threadIdx.x; l < kMaxDefer; l += 64) {
         st->seal[slot].pl[l] = l < kb ? st->pl[l] : -1;
         st->seal[slot].qs[l] = st->qs[l];
@@ -2914,6 +2985,17 @@ static size_t pass_lds_env() {
     return v > 0 && v <= 150 * 1024 ? (size_t)v : 0;
 }
 
+// The form-23 instance (pass_q_kernel) runs for this session's passes (K = 64 blocks, ldc == 64
+// exactly: the kernel addresses C with 64 steps per row; a band within one 2 GiB descriptor)
+static bool pass_q_runs(const Geometry& g, const Defer& d, int rb) {
+    return d.form == 23 && d.K == 64 && d.ldc == 64 && (int64_t)rb * g.ld * 8 < ((int64_t)1 << 31) && rb <= 1024;
+}
+// DLP_PASS_SADDR=0 (A/B): every LDS-DMA of the form-23 pass in the clamped per-lane form
+static bool pass_saddr_env() {
+    static const int v = std::getenv("DLP_PASS_SADDR") ? std::atoi(std::getenv("DLP_PASS_SADDR")) : 1;
+    return v != 0;
+}
+
 template <bool NT, int K>
 static hipError_t pass(const Geometry& g, const Defer& d, DevState* st, int rb, int occ,
                        hipStream_t s, double* Tout, int seal, uint32_t* bcnt) {
@@ -2993,8 +3075,7 @@ static hipError_t pass(const Geometry& g, const Defer& d, DevState* st, int rb, 
             return hipGetLastError();
         }
     }
-    if (d.form == 23 && K == 64 && d.K == 64 && d.ldc == 64 && (int64_t)rb * g.ld * 8 < ((int64_t)1 << 31) &&
-        rb <= 1024) {
+    if (K == 64 && pass_q_runs(g, d, rb)) {
         // LDS-ring DPP pass (K = 64 blocks; 256-column tiles): 2 rows per group, 4 groups in
         // flight per wave: 32 KiB of ring + 4 KiB of row classes per workgroup, so three pass
         // workgroups leave the lookahead chain's LDS free on a CU
@@ -3008,57 +3089,53 @@ static hipError_t pass(const Geometry& g, const Defer& d, DevState* st, int rb, 
             static const int qu_env = std::getenv("DLP_Q_U") ? std::atoi(std::getenv("DLP_Q_U")) : 0;
             // groups holding dense pivot rows stay on the DPP chain (DLP_PASS_PIVG=0: the row-by-row replay)
             static const int pivg = std::getenv("DLP_PASS_PIVG") ? std::atoi(std::getenv("DLP_PASS_PIVG")) : 1;
+            const bool sad = pass_saddr_env();
             const int qu = qu_env == 2 || qu_env == 4 ? qu_env : (g.rows >= 16384 ? 4 : 2);
             constexpr int U = 2;
             const int D = qd == 2 || qd == 3 || qd == 6 || qd == 8 ? qd : 4;
+            const dim3 grid((unsigned)((g.width + 255) / 256), (unsigned)((g.rows + rb - 1) / rb));
+            // the instance of (U, D): publishing or not, scalar-base DMAs or per-lane ones
+#define DLP_PASS_Q(UU, DD, DYN)                                                                                \
+    do {                                                                                                       \
+        if (bcnt && sad)                                                                                       \
+            pass_q_kernel<NT, UU, DD, true, true><<<grid, 256, DYN, s>>>(g.T, To, g.ld, g.rows, g.width, bd, d.C, \
+                                                                         d.ldc, d.P, d.nzc, rb, bcnt, pivg);  \
+        else if (bcnt)                                                                                         \
+            pass_q_kernel<NT, UU, DD, false, true><<<grid, 256, DYN, s>>>(g.T, To, g.ld, g.rows, g.width, bd, d.C, \
+                                                                          d.ldc, d.P, d.nzc, rb, bcnt, pivg); \
+        else if (sad)                                                                                          \
+            pass_q_kernel<NT, UU, DD, true, false><<<grid, 256, DYN, s>>>(g.T, To, g.ld, g.rows, g.width, bd, d.C, \
+                                                                          d.ldc, d.P, d.nzc, rb, nullptr, pivg); \
+        else                                                                                                   \
+            pass_q_kernel<NT, UU, DD, false, false><<<grid, 256, DYN, s>>>(g.T, To, g.ld, g.rows, g.width, bd, d.C, \
+                                                                           d.ldc, d.P, d.nzc, rb, nullptr, pivg); \
+    } while (0)
             if (qu == 4) {
                 const int D4 = qd == 3 ? 3 : 2;
                 size_t dyn4 = std::max((size_t)4 * D4 * 128 * 4 * sizeof(double), pass_lds_env());
                 if (occ > 0) dyn4 = std::max(dyn4, (size_t)160 * 1024 / occ - 1024 * sizeof(int32_t));
-                const dim3 grid4((unsigned)((g.width + 255) / 256), (unsigned)((g.rows + rb - 1) / rb));
                 if (g.rows > 0) {
-                    if (D4 == 3) {
-                        if (bcnt)
-                            pass_q_kernel<NT, 4, 3, true><<<grid4, 256, dyn4, s>>>(g.T, To, g.ld, g.rows, g.width, bd,
-                                                                                d.C, d.ldc, d.P, d.nzc, rb, bcnt, pivg);
-                        else
-                            pass_q_kernel<NT, 4, 3><<<grid4, 256, dyn4, s>>>(g.T, To, g.ld, g.rows, g.width, bd, d.C,
-                                                                          d.ldc, d.P, d.nzc, rb, nullptr, pivg);
-                    } else {
-                        if (bcnt)
-                            pass_q_kernel<NT, 4, 2, true><<<grid4, 256, dyn4, s>>>(g.T, To, g.ld, g.rows, g.width, bd,
-                                                                                d.C, d.ldc, d.P, d.nzc, rb, bcnt, pivg);
-                        else
-                            pass_q_kernel<NT, 4, 2><<<grid4, 256, dyn4, s>>>(g.T, To, g.ld, g.rows, g.width, bd, d.C,
-                                                                          d.ldc, d.P, d.nzc, rb, nullptr, pivg);
-                    }
+                    if (D4 == 3)
+                        DLP_PASS_Q(4, 3, dyn4);
+                    else
+                        DLP_PASS_Q(4, 2, dyn4);
                 }
                 if (seal < 0) blk_reset_kernel<<<1, 64, 0, s>>>(st);
                 return hipGetLastError();
             }
             size_t dyn = std::max((size_t)4 * D * 128 * U * sizeof(double), pass_lds_env());
             if (occ > 0) dyn = std::max(dyn, (size_t)160 * 1024 / occ - 1024 * sizeof(int32_t));
-            const dim3 grid((unsigned)((g.width + 255) / 256), (unsigned)((g.rows + rb - 1) / rb));
-#define DLP_PASS_Q(DD)                                                                                     \
-    do {                                                                                                   \
-        if (bcnt)                                                                                          \
-            pass_q_kernel<NT, U, DD, true><<<grid, 256, dyn, s>>>(g.T, To, g.ld, g.rows, g.width, bd, d.C, \
-                                                                  d.ldc, d.P, d.nzc, rb, bcnt, pivg);     \
-        else                                                                                               \
-            pass_q_kernel<NT, U, DD><<<grid, 256, dyn, s>>>(g.T, To, g.ld, g.rows, g.width, bd, d.C, d.ldc, \
-                                                           d.P, d.nzc, rb, nullptr, pivg);                 \
-    } while (0)
             if (g.rows > 0) {
                 if (D == 2)
-                    DLP_PASS_Q(2);
+                    DLP_PASS_Q(U, 2, dyn);
                 else if (D == 3)
-                    DLP_PASS_Q(3);
+                    DLP_PASS_Q(U, 3, dyn);
                 else if (D == 6)
-                    DLP_PASS_Q(6);
+                    DLP_PASS_Q(U, 6, dyn);
                 else if (D == 8)
-                    DLP_PASS_Q(8);
+                    DLP_PASS_Q(U, 8, dyn);
                 else
-                    DLP_PASS_Q(4);
+                    DLP_PASS_Q(U, 4, dyn);
             }
 #undef DLP_PASS_Q
             if (seal < 0) blk_reset_kernel<<<1, 64, 0, s>>>(st);
@@ -3181,9 +3258,10 @@ hipError_t launch_flush_defer(const Geometry& g, const Defer& d, DevState* st, b
     uint32_t* bcnt = nullptr;
     if (bp && bp->cnt && seal >= 0 && Tout && Tout != g.T && band_pub_ok(*bp, g, d, rows_per_block))
         bcnt = bp->cnt + seal * bp->stride;
-    if (g.rows > 0 && d.C && d.nzc) {
-        drop_failed_step_kernel<<<(unsigned)((g.rows + 256) / 256), 256, 0, s>>>(
-            st, seal >= 0 ? &st->seal[seal].blk : &st->blk, d.C, d.ldc, d.nzc, g.rows);
+    // (a sealed block's failed step was dropped by its seal: launch_seal_defer)
+    if (seal < 0 && g.rows > 0 && d.C && d.nzc) {
+        drop_failed_step_kernel<<<(unsigned)((g.rows + 256) / 256), 256, 0, s>>>(st, &st->blk, d.C, d.ldc, d.nzc,
+                                                                                g.rows);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -3215,10 +3293,12 @@ hipError_t launch_reset_cols(const Geometry& g, const DevState* st, int seal, hi
     return hipGetLastError();
 }
 
-hipError_t launch_seal_defer(DevState* st, int slot, hipStream_t s, const BandPub* bp) {
+hipError_t launch_seal_defer(const Geometry& g, const Defer& d, DevState* st, int slot, hipStream_t s,
+                             const BandPub* bp) {
     if (slot < 0 || slot > 1) return hipErrorInvalidValue;
+    const bool drop = g.rows > 0 && d.C && d.nzc;   // (launch_flush_defer's condition for the in-place path)
     seal_kernel<<<1, 64, 0, s>>>(st, slot, bp && bp->cnt ? bp->cnt + slot * bp->stride : nullptr,
-                                 bp ? bp->stride : 0);
+                                 bp ? bp->stride : 0, drop ? d.C : nullptr, d.ldc, drop ? d.nzc : nullptr, g.rows);
     return hipGetLastError();
 }
 

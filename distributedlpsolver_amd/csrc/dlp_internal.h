@@ -320,8 +320,11 @@ bool lookahead_form(int form);
 hipError_t chain_stamps_enable();
 hipError_t chain_stamps_dump(uint64_t* host64x16);
 hipError_t chain_wg_stamps_dump(uint64_t* host1024x8);
-// End of a lookahead block: st->seal[slot] := (blk, pl), blk := 0.
-hipError_t launch_seal_defer(DevState* st, int slot, hipStream_t s, const BandPub* bp = nullptr);
+// End of a lookahead block: st->seal[slot] := (blk, pl), blk := 0.  d: the block's arrays; a step
+// that failed (DLP_UNBOUNDED) is dropped from them here, so the sealed block's pass
+// (launch_flush_defer with seal >= 0) finds the zeroed tail it expects.
+hipError_t launch_seal_defer(const Geometry& g, const Defer& d, DevState* st, int slot, hipStream_t s,
+                             const BandPub* bp = nullptr);
 hipError_t launch_prow(const Geometry& g, const DevState* st, int64_t* prow_bits, int nranks,
                        hipStream_t s);
 hipError_t launch_update(const Geometry& g, const double* colq, const double* prow,

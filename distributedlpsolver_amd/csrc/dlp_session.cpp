@@ -1208,7 +1208,7 @@ dlp::BandPub band_pub(const dlp_session* s) {
 // this pass (a window's end).
 int la_block_end(dlp_session* s, bool drain, hipEvent_t* evp) {
     const dlp::BandPub bp = band_pub(s);
-    HIP_TRY(dlp::launch_seal_defer(s->st, s->cur, s->stream, &bp));
+    HIP_TRY(dlp::launch_seal_defer(s->g, s->dslot[s->cur], s->st, s->cur, s->stream, &bp));
     HIP_TRY(hipEventRecord(s->ev_seal, s->stream));
     HIP_TRY(hipStreamWaitEvent(s->pstream, s->ev_seal, 0));
     if (evp) HIP_TRY(hipEventRecord(evp[0], s->pstream));
