@@ -1,7 +1,7 @@
 # Build of the MI355X-native simplex (gfx950 only) and its CPU oracle.
 #   make            -> distributedlpsolver_amd/libdlp.so + oracle/liboracle.so
 #   make ref        -> oracle/_ref/dlp_ref (reference built from its own sources; container only)
-#   make asm        -> build/dlp_kernels-gfx950.s (ISA audit)
+#   make asm        -> build/dlp_kernels-gfx950.s (ISA audit); any unit: make build/dlp_pass-gfx950.s
 ROCM      ?= /opt/rocm
 HIPCC     ?= $(ROCM)/bin/hipcc
 ARCH      ?= gfx950
@@ -11,7 +11,7 @@ HIPFLAGS  := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Iinc
              -Wall -Wno-unused-function
 LIBDLP    := $(PKG)/libdlp.so
 OBJS      := build/dlp_kernels.o build/dlp_batched.o build/dlp_mw.o build/dlp_session.o build/dlp_adalloc.o \
-             build/dlp_instance.o build/dlp_general.o build/dlp_defer.o build/dlp_cluster.o build/dlp_reopt.o \
+             build/dlp_instance.o build/dlp_general.o build/dlp_chain.o build/dlp_pass.o build/dlp_cluster.o build/dlp_reopt.o \
              build/dlp_dual.o
 
 all: $(LIBDLP) oracle tools
@@ -19,7 +19,9 @@ all: $(LIBDLP) oracle tools
 build:
 	mkdir -p build
 
-build/%.o: $(CSRC)/%.hip $(CSRC)/dlp_internal.h $(CSRC)/dlp_device.h include/dlp.h | build
+HIPDEPS   := $(CSRC)/dlp_internal.h $(CSRC)/dlp_device.h $(CSRC)/dlp_defer_device.h $(CSRC)/dlp_host.h include/dlp.h
+
+build/%.o: $(CSRC)/%.hip $(HIPDEPS) | build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 build/%.o: $(CSRC)/%.cpp $(CSRC)/dlp_internal.h $(CSRC)/dlp_host.h include/dlp.h include/distributed_solver/instance.h | build
@@ -34,8 +36,10 @@ oracle:
 ref:
 	$(MAKE) -C oracle ref
 
-asm: | build
-	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S $(CSRC)/dlp_kernels.hip -o build/dlp_kernels-gfx950.s
+asm: build/dlp_kernels-gfx950.s
+
+build/%-gfx950.s: $(CSRC)/%.hip $(HIPDEPS) | build
+	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S $< -o $@
 
 clean:
 	rm -rf build $(LIBDLP)

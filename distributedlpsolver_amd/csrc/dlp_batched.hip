@@ -1300,7 +1300,7 @@ extern "C" int dlp_batched_occupancy(int64_t m, int64_t n, int device, int32_t* 
     if (m <= 0 || n <= 0) return DLP_ERR_ARG;
     const size_t lds = sizeof(double) * ((m + 1) * (n + 1) + (m + 1) + (n + 1)) + sizeof(int32_t) * (n + m + 8) +
                        sizeof(double) * 2 + 16;
-    static const bool force_lds = std::getenv("DLP_BATCH_LDS") && std::atoi(std::getenv("DLP_BATCH_LDS")) == 1;
+    static const bool force_lds = dlp::env_int("DLP_BATCH_LDS", 0) == 1;
     const int nw = (int)((n + 63) / 64);
     const bool reg = !force_lds && m == 64 && nw >= 1 && nw <= 3;
     if (!reg && lds > 160 * 1024) return DLP_ERR_UNSUPPORTED;
@@ -1521,7 +1521,7 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
         }
         // m = 64 with n <= 192 columns: the register-resident kernel (DLP_BATCH_LDS=1: the LDS
         // kernel, for A/B); otherwise the LDS-resident one
-        static const bool force_lds = std::getenv("DLP_BATCH_LDS") && std::atoi(std::getenv("DLP_BATCH_LDS")) == 1;
+        static const bool force_lds = dlp::env_int("DLP_BATCH_LDS", 0) == 1;
         const int nw = (int)((n + 63) / 64);
         // (the dual re-solve has an LDS instantiation only: m = 64 goes through it for that call,
         // on the same records)

@@ -1,0 +1,73 @@
+// dlp_defer_device.h — device-side helpers shared by the two deferred rank-k units, the
+// selection chain (dlp_chain.hip) and the tableau pass (dlp_pass.hip): bit casts for buffer
+// operands, (non)temporal vector loads / stores, the asm LDS-DMA and its counted waits.
+// Internal; included after dlp_device.h inside `namespace dlp { namespace { ... } }`.
+#pragma once
+
+typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+typedef unsigned int u2v __attribute__((ext_vector_type(2)));
+// A double's bits as the b64 buffer-store operand, built from scalars: hipcc miscompiles a
+// __builtin_bit_cast of an element of an ext_vector value (tests/test_isa.py source guard).
+__device__ __forceinline__ u2v dbits(double v) {
+    uint64_t u;
+    __builtin_memcpy(&u, &v, sizeof(u));
+    u2v w;
+    w.x = (unsigned)u;
+    w.y = (unsigned)(u >> 32);
+    return w;
+}
+
+template <bool NT>
+__device__ inline d2 ldv(const double* p) {
+    if constexpr (NT)
+        return __builtin_nontemporal_load((const d2*)p);
+    else
+        return *(const d2*)p;
+}
+template <bool NT>
+__device__ inline double ldv1(const double* p) {
+    if constexpr (NT)
+        return __builtin_nontemporal_load(p);
+    else
+        return *p;
+}
+template <bool NT>
+__device__ inline void stv1(double* p, double v) {
+    if constexpr (NT)
+        __builtin_nontemporal_store(v, p);
+    else
+        *p = v;
+}
+template <bool NT>
+__device__ inline void stv(double* p, d2 v) {
+    if constexpr (NT)
+        __builtin_nontemporal_store(v, (d2*)p);
+    else
+        *(d2*)p = v;
+}
+
+// 16-B LDS-DMA (global_load_lds_dwordx4: lane x's 16 bytes land at the wave-uniform LDS
+// address m0 + 16 x) issued from inline asm, so that hipcc does not count it: with the
+// builtin it waits vmcnt(0) before the next LDS read or ordinary-load use, draining every
+// DMA in flight (cdna_hip_programming.md, glds).  The callers retire their DMAs with counted
+// waits of their own (vmwait), which hold because between two of them they issue no other
+// vector-memory instruction, or a fixed number of them.  The lgkmcnt(0) orders the DMA's
+// LDS write after this wave's earlier LDS reads of the slot it refills.
+__device__ __forceinline__ void glds16(const void* g, uint32_t m0) {
+    asm volatile("s_waitcnt lgkmcnt(0)\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "{m0}"(m0) : "memory");
+}
+// The same DMA in the scalar-base form: lane x reads 16 B at base + voff (voff: unsigned 32-bit bytes),
+// the wave-uniform base in an SGPR pair, so a stream that only advances by a uniform stride needs no
+// per-lane address arithmetic.  The s_nop covers a base that an SALU add has just written (the
+// compiler pads nothing inside the statement).
+__device__ __forceinline__ void glds16s(uint32_t voff, const void* base, uint32_t m0) {
+    asm volatile("s_nop 4\n\ts_waitcnt lgkmcnt(0)\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "{m0}"(m0)
+                 : "memory");
+}
+template <int N>
+__device__ __forceinline__ void vmwait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+__device__ __forceinline__ uint32_t lds_addr(const void* p) {
+    return __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p);
+}
+
+constexpr int kAuxSc1 = 16;   // buffer-op cache policy: sc1 (write-through store / L2 load)

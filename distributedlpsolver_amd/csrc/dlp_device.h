@@ -1,5 +1,5 @@
 // dlp_device.h — device-side helpers shared by the pivot kernels
-// (dlp_kernels.hip) and the deferred rank-k kernels (dlp_defer.hip):
+// (dlp_kernels.hip) and the deferred rank-k kernels (dlp_chain.hip, dlp_pass.hip):
 // pricing / candidate reductions with index tie-breaks, select + pivot log.
 // Internal; included inside `namespace dlp { namespace { ... } }`.
 #pragma once

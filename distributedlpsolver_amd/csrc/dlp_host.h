@@ -1,6 +1,7 @@
 // dlp_host.h — host-side objects behind the C ABI (not public).
 #pragma once
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -60,6 +61,18 @@ int build_stdform(const General& g, StdForm* out);
 int parse_mps(const char* path, General* out);
 
 void set_error(const std::string& msg);
+
+// An integer tuning knob or test hook from the environment: atoi / atol of the variable when it
+// is set (so unparsable text reads as 0), else the default.  Reads the environment on every call;
+// a call site that wants a read-once knob keeps the value in a `static const` of its own.
+inline int env_int(const char* name, int dflt) {
+    const char* e = std::getenv(name);
+    return e ? std::atoi(e) : dflt;
+}
+inline long env_long(const char* name, long dflt) {
+    const char* e = std::getenv(name);
+    return e ? std::atol(e) : dflt;
+}
 
 }  // namespace dlp
 

@@ -153,7 +153,7 @@ struct XPeers {
 // Block size (bytes) and offsets for nranks ranks, row length ld and nslot slots per sender.
 size_t xblock_layout(int nranks, int64_t ld, int nslot, XPeers* xp);
 
-// Deferred rank-k update (dlp_defer.hip).  Up to K pivots are selected against
+// Deferred rank-k update (dlp_chain.hip selects, dlp_pass.hip applies).  Up to K pivots are selected against
 // the stale HBM tableau T0 through "replayed" views (column q and pivot row p
 // re-derived by applying the block's earlier steps, in order, with the same
 // fma / overwrite / skip per element as the eager update); the objective row
@@ -169,13 +169,13 @@ struct Defer {
     double* P = nullptr;   // K x ld: normalised pivot rows
     double* rhs = nullptr; // rows: current RHS column (eager cache)
     int32_t* nzc = nullptr; // rows: nonzero C[i][l] of the block so far (the pass's row class)
-    int form = 3;          // pass kernel, LDS-staged coefficients: 0 = 2 doubles/lane,
-                           // 1 = 1 double/lane x 2 rows, 2 = 1 double/lane x 4 rows;
-                           // scalar-coefficient forms: 3 = 1 double x 4 rows (default; 4 at K = 32 streaming),
-                           // 4 = 2 doubles x 2 rows, 5 = 1 double x 8 rows
+    int form = 3;          // pass kernel, 0-23: pass<NT, K> (dlp_pass.hip) maps each form to its kernel
+                           // instance, DESIGN.md §11 describes them.  0-2 stage the coefficients in
+                           // LDS, 3-5 and 20 read them as scalars (3 = 1 double x 4 rows, the default),
+                           // 6-19 stream bands, 21 / 23 are the DPP passes at K = 64, 22 the MFMA pass
 };
 
-// Lookahead band publication: the form-21 pass of seal slot s counts its
+// Lookahead band publication: the form-21 / 22 / 23 pass of seal slot s counts its
 // finished workgroups per band in cnt[s * stride + band]; a band whose count reached ntiles
 // is final in Tn, so the next block's selections read its rows there and replay only their
 // own block (bit-identical: the pass computes the same operations in the same order).
@@ -258,7 +258,7 @@ hipError_t launch_carry_in(const Geometry& g, const int64_t* in, DevState* st, i
                            hipStream_t s);
 hipError_t launch_set_status(DevState* st, int status, hipStream_t s);
 
-// Deferred launchers (dlp_defer.hip).  Pricing tiles are kDeferTile columns.
+// Deferred selection launchers (dlp_chain.hip).  Pricing tiles are kDeferTile columns.
 // prev / prev_seal (lookahead): the sealed block st->seal[prev_seal] whose arrays are
 // `prev` is not yet applied to g.T; its steps are replayed before the current block's.
 // bp (lookahead at K = 64): the pass in flight publishes its finished bands (BandPub).
@@ -307,7 +307,7 @@ hipError_t launch_commit_defer(const Geometry& g, const Defer& d, DevState* st,
                                const int64_t* prow_bits, PricePart* pp, double tol_dj,
                                dlp_pivot* log, int64_t log_cap, hipStream_t s,
                                const XPeers* xp = nullptr, uint32_t seq = 0);
-// The tableau pass: applies the block's st->blk steps to rows [0, rows), then blk = 0.
+// The tableau pass (dlp_pass.hip): applies the block's st->blk steps to rows [0, rows), then blk = 0.
 // Lookahead (seal >= 0): the block st->seal[seal], read from g.T and written to Tout
 // (every row, untouched ones copied; blk is left alone).  Only the forms with an
 // out-of-place instance: lookahead_form() is the single source of truth (3, 4, 5, 20, 21,
@@ -316,11 +316,11 @@ hipError_t launch_flush_defer(const Geometry& g, const Defer& d, DevState* st, b
                               int rows_per_block, int occupancy, hipStream_t s,
                               double* Tout = nullptr, int seal = -1, const BandPub* bp = nullptr);
 bool lookahead_form(int form);
-// Diagnostics (DLP_CHAIN_STAMPS): phase stamps of the LEAN chain kernels (dlp_defer.hip).
+// Diagnostics (DLP_CHAIN_STAMPS): phase stamps of the LEAN chain kernels (dlp_chain.hip).
 hipError_t chain_stamps_enable();
 hipError_t chain_stamps_dump(uint64_t* host64x16);
 hipError_t chain_wg_stamps_dump(uint64_t* host1024x8);
-// End of a lookahead block: st->seal[slot] := (blk, pl), blk := 0.  d: the block's arrays; a step
+// End of a lookahead block (dlp_pass.hip): st->seal[slot] := (blk, pl), blk := 0.  d: the block's arrays; a step
 // that failed (DLP_UNBOUNDED) is dropped from them here, so the sealed block's pass
 // (launch_flush_defer with seal >= 0) finds the zeroed tail it expects.
 hipError_t launch_seal_defer(const Geometry& g, const Defer& d, DevState* st, int slot, hipStream_t s,

@@ -138,7 +138,7 @@ struct dlp_session {
     int64_t phase1_pivots = 0;
     enum StepKind { STEP_PIVOT, STEP_FORCED, STEP_CARRY } step_kind = STEP_PIVOT;
     bool step_void = false;
-    // deferred rank-k update (dlp_defer.hip): block arrays, pivots enqueued since
+    // deferred rank-k update (dlp_chain.hip, dlp_pass.hip): block arrays, pivots enqueued since
     // the last tableau pass, pass geometry; update-kernel launch accounting
     dlp::Defer d;
     int since_flush = 0;
@@ -625,15 +625,13 @@ int flush_pending_block(dlp_session* s);
 // Condensed tableau by default (dlp_options.condensed = 0); DLP_CONDENSED=0 / 1 overrides the
 // auto choice (A/B and tests).
 bool condensed_auto() {
-    static const int v = std::getenv("DLP_CONDENSED") ? std::atoi(std::getenv("DLP_CONDENSED")) : 1;
+    static const int v = dlp::env_int("DLP_CONDENSED", 1);
     return v == 1;
 }
 
 int ratio_threads_policy(const dlp_session* s) {
-    if (const char* e = std::getenv("DLP_RATIO_THREADS")) {
-        const int n = std::atoi(e);
-        if (n == 64 || n == 128 || n == 256) return n;
-    }
+    const int n = dlp::env_int("DLP_RATIO_THREADS", 0);
+    if (n == 64 || n == 128 || n == 256) return n;
     const int64_t per_rank = s->m / std::max(s->nranks, 1);
     return per_rank <= 8192 ? 128 : dlp::kRatioDeferThreads;
 }
@@ -926,14 +924,12 @@ int session_init(const dlp_problem* prob, const dlp_options* opt, int rank, int 
              (opt->small_lp == 0 && K == 0 && tiny && variant_auto))) {
             s->cl_wg = dlp::cluster_plan(s->m, s->N, cus, &s->cl_cw);
             // tuning only: DLP_CLUSTER_WG=G forces the workgroup count (if the slices fit)
-            if (const char* e = std::getenv("DLP_CLUSTER_WG")) {
-                const int gw = std::atoi(e);
-                const int cw = gw > 0 ? (int)((s->N + gw) / gw) : 0;
-                if (gw > 0 && gw <= cus && (int64_t)(gw - 1) * cw < s->N + 1 &&
-                    dlp::cluster_lds_bytes(s->m, cw) <= 160 * 1024 - 1024) {
-                    s->cl_wg = gw;
-                    s->cl_cw = cw;
-                }
+            const int gw = dlp::env_int("DLP_CLUSTER_WG", 0);
+            const int cw = gw > 0 ? (int)((s->N + gw) / gw) : 0;
+            if (gw > 0 && gw <= cus && (int64_t)(gw - 1) * cw < s->N + 1 &&
+                dlp::cluster_lds_bytes(s->m, cw) <= 160 * 1024 - 1024) {
+                s->cl_wg = gw;
+                s->cl_cw = cw;
             }
             s->cluster = s->cl_wg > 0;
         }
@@ -1191,7 +1187,7 @@ int la_drain(dlp_session* s) {
 // finished workgroups per band; the next block's selections read a finished band's rows
 // from the pass's output (Tn) and replay their own block only.  DLP_BAND_PUB=0: off (A/B).
 dlp::BandPub band_pub(const dlp_session* s) {
-    static const bool off = std::getenv("DLP_BAND_PUB") && std::atoi(std::getenv("DLP_BAND_PUB")) == 0;
+    static const bool off = dlp::env_int("DLP_BAND_PUB", 1) == 0;
     dlp::BandPub b;
     if (!s->band_cnt || off) return b;
     b.cnt = s->band_cnt;
@@ -1269,8 +1265,7 @@ int flush_pending_block(dlp_session* s) {
 // (DLP_RCCL_LOOKAHEAD=1).  A caller's explicit lookahead setting is kept.
 bool rccl_lookahead_ok(const dlp_session* s) {
     if (s->nranks == 1) return true;
-    const char* e = std::getenv("DLP_RCCL_LOOKAHEAD");
-    return e && std::atoi(e) == 1;
+    return dlp::env_int("DLP_RCCL_LOOKAHEAD", 0) == 1;
 }
 
 int la_policy(dlp_session* s) {
@@ -1289,8 +1284,7 @@ int la_policy(dlp_session* s) {
 
 // DLP_PEER_ONELAUNCH=1: a peer pivot as one launch (read per pivot, so tests can switch it)
 bool peer_onelaunch() {
-    const char* e = std::getenv("DLP_PEER_ONELAUNCH");
-    return e && std::atoi(e) == 1;
+    return dlp::env_int("DLP_PEER_ONELAUNCH", 0) == 1;
 }
 
 // The one-launch peer pivot applies: 256-lane ratio workgroups, or 128-lane ones when the chain owns
@@ -2067,10 +2061,10 @@ int solve_in_process_once(const dlp_problem* prob, const dlp_options& o, int P, 
         });
     if (res == DLP_OK) {
         res = on_ranks([&](int r) {
-            if (const char* e = std::getenv("DLP_TEST_FAIL_RANK"))   // tests: fail this rank's 2nd poll
-                if (std::atoi(e) == r) ss[r]->fault_after_polls = 1;
-            if (const char* e = std::getenv("DLP_TEST_FAIL_PEER_RANK"))   // the same, on the peer exchange only
-                if (std::atoi(e) == r && ss[r]->xmode == dlp_session::X_PEER) ss[r]->fault_after_polls = 1;
+            // tests: fail this rank's 2nd poll; the same, on the peer exchange only (ranks are >= 0)
+            if (dlp::env_int("DLP_TEST_FAIL_RANK", -1) == r) ss[r]->fault_after_polls = 1;
+            if (dlp::env_int("DLP_TEST_FAIL_PEER_RANK", -1) == r && ss[r]->xmode == dlp_session::X_PEER)
+                ss[r]->fault_after_polls = 1;
             int64_t done = 0;
             return dlp_session_run(ss[r], o.max_pivots, &done);
         });
@@ -2336,8 +2330,7 @@ void make_xrec(dlp_session* s, XRec* me) {
         me->ok = 0;
         std::snprintf(me->why, sizeof(me->why), "%s", w.c_str());
     };
-    if (const char* e = std::getenv("DLP_TEST_PEER_FAIL"))
-        if (std::atoi(e) == s->rank) fail("injected (DLP_TEST_PEER_FAIL)");
+    if (dlp::env_int("DLP_TEST_PEER_FAIL", -1) == s->rank) fail("injected (DLP_TEST_PEER_FAIL)");
     if (me->ok && ensure_xblock(s) != DLP_OK) fail(std::string("exchange block: ") + dlp_last_error());
     if (me->ok) {
         hipIpcMemHandle_t h;

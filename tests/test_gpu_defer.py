@@ -1,4 +1,4 @@
-"""Deferred rank-k update (dlp_defer.hip) against the eager rank-1 path and the
+"""Deferred rank-k update (dlp_chain.hip, dlp_pass.hip) against the eager rank-1 path and the
 oracle, bit for bit.  K pivots are selected on replayed views of the stale
 tableau and applied in one pass; every element must see exactly the eager
 sequence of fma / overwrite / skip, so pivot logs, x, y, basis and the whole

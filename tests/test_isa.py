@@ -1,6 +1,6 @@
 """ISA audit of the shipped code object (CPU test, no GPU needed).
 
-The form-21 tableau pass (dlp_defer.hip, pass_d_kernel) issues v_fmac_f64_dpp
+The form-21 tableau pass (dlp_pass.hip, pass_d_kernel) issues v_fmac_f64_dpp
 from inline asm, where the compiler's hazard recognizer cannot see it.  gfx9
 requires two wait states between a VALU write of a VGPR and a DPP read of it;
 the kernel is written so that the DPP source (a coefficient register) is only
