@@ -1026,6 +1026,31 @@ __device__ __forceinline__ void vmwait_group(int g) {
         default: vmwait<U * (D - 1) + 6 * U>(); break;
     }
 }
+// The same wait under a shared coefficient ring (pass_q_kernel, CS): a group is U / 2 tableau DMAs and
+// U stores, and the first group of every supergroup of G issues U / 2 coefficient DMAs ahead of them
+// (behind its own wait).  Newer than group g's tableau DMAs: the D - 1 groups between, and the
+// coefficient DMAs of a supergroup that opened among them: when g lies 1 .. D - 1 past a supergroup's
+// start (p = g % G; D <= G, so at most one).  The coefficient DMAs of g's own supergroup are older
+// than its first group's tableau DMAs, so that group's wait covers them.
+template <int D, int U>
+__device__ __forceinline__ void vmwait_group_cs(int g, int p) {
+    constexpr int h = U / 2;
+    static_assert(D >= 2 && D <= 4 && 3 * h * (D - 1) + h <= 63, "vmcnt holds 6 bits");
+    if (g >= D - 1) {
+        if (p >= 1 && p <= D - 1)
+            vmwait<3 * h * (D - 1) + h>();
+        else
+            vmwait<3 * h * (D - 1)>();
+        return;
+    }
+    // the prologue's groups still to come, the finished groups, supergroup 1's coefficients (g >= 1)
+    if (g == 0)
+        vmwait<h * (D - 1)>();
+    else if (g == 1)
+        vmwait<h * (D > 2 ? D - 2 : 0) + 3 * h + h>();
+    else
+        vmwait<h * (D > 3 ? D - 3 : 0) + 6 * h + h>();
+}
 template <int U, int L>
 __device__ __forceinline__ void ring_step(double (&t)[U], const double (&c)[U][2], const double (&pr)[64]) {
     constexpr int e = L & 1, n = (L & 31) >> 1;
@@ -1075,8 +1100,19 @@ __device__ __forceinline__ double redo_pivot_row(const double* cr, int cl, const
 // PUB: band publication as form 21's (pass_d_kernel)
 // pivg: groups of dense and dense pivot rows run the chain too (DLP_PASS_PIVG, default 1)
 // SA: the LDS-DMAs in the scalar-base form (DLP_PASS_SADDR, default 1)
+// CS (with SA): the coefficient rows fetched once per workgroup (DLP_PASS_CSHARE).  The four waves of a
+// workgroup run the same rows of the band, so their coefficient DMAs are the same 512 B per row four
+// times over.  Here each wave keeps a private ring of D tableau slots (U rows x 64 columns), and the
+// workgroup shares one coefficient ring behind them: NS = 2 slots of a supergroup of G = 4 consecutive
+// groups (G U rows x 64 coefficients).  Wave w fetches group G sg + w of supergroup sg, U / 2 DMAs, all
+// waves at the same place: behind the barrier that opens supergroup sg - 1.  One barrier per
+// supergroup: every wave waits for its own DMAs of supergroup sg (the counted wait of the
+// supergroup's first group covers them, vmwait_group_cs), then the barrier, then reads any wave's
+// rows; the same barrier says that every wave is done with supergroup sg - 1, whose slot is refilled
+// behind it.  A bare s_barrier: __syncthreads() would drain the ring and the stores.  Every wave of a
+// workgroup runs the same ng groups on every path, so the barriers match.
 // (three waves per SIMD, at most 168 VGPRs, as before the pivot-row recompute was added)
-template <bool NT, int U, int D, bool SA = false, bool PUB = false>
+template <bool NT, int U, int D, bool SA = false, bool CS = false, bool PUB = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void pass_q_kernel(
                                                      const double* __restrict__ T, double* __restrict__ Tout,
                                                      int64_t ld, int64_t rows, int64_t width,
@@ -1085,12 +1121,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void p
                                                      const double* __restrict__ P,
                                                      const int32_t* __restrict__ nzc, int rb,
                                                      uint32_t* bcnt = nullptr, int pivg = 0) {
-    constexpr int K = 64, SLOT = 128 * U;   // doubles per ring slot
+    constexpr int K = 64, SLOT = (CS ? 64 : 128) * U;   // doubles per ring slot
+    constexpr int G = 4, NS = 2;                          // CS: groups per supergroup, supergroup slots
+    static_assert(!CS || (SA && G == 4 && D <= G), "one group per wave; the shared ring's counted waits");
     constexpr int kSt = (NT ? 2 : 0) | (PUB ? kAuxSc1 : 0);   // store policy
     static_assert(U % 2 == 0, "one DMA carries two rows");
     __shared__ __attribute__((aligned(16))) int32_t cls[1024];
     typedef int32_t clsv __attribute__((ext_vector_type(U)));
-    extern __shared__ double ring[];   // [4 waves][D slots][SLOT]
+    extern __shared__ double ring[];   // [4 waves][D slots][SLOT]; CS: then [NS][G groups][U rows][64]
     const int kb = bd->blk;
     const bool outplace = Tout != T;
     if (kb == 0 && !outplace) return;   // full and partial blocks alike (zeroed tails)
@@ -1119,6 +1157,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void p
     const int64_t wcc = wc < ld - 1 ? wc : ld - 2;
     double* wbase = ring + (size_t)w * D * SLOT;
     const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)wbase;
+    const double* cring = ring + (size_t)4 * D * SLOT;
+    const uint32_t cbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)cring;
     // SA: every DMA in the scalar-base form (glds16s).  The base is the DMA's first row, wave-uniform;
     // the lane's byte offset is fixed for the band: its row of the pair and its clamped column
     // (tvoff; ld * 8 + wcc * 8 < 2^32 since rb * ld * 8 < 2^31), its 16 B of the pair's 128
@@ -1152,6 +1192,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void p
                 glds16(tsrc + (int64_t)r * ld, m0);
             }
         }
+        if constexpr (CS) return;
 #pragma unroll
         for (int k = 0; k < U / 2; ++k) {
             const uint32_t m0 = __builtin_amdgcn_readfirstlane(lbase + s * SLOT * 8 + U * 512 + k * 1024);
@@ -1175,10 +1216,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void p
         for (int k = 0; k < U / 2; ++k)
             glds16s(tvoff, tb + (int64_t)2 * k * ld * 8,
                     __builtin_amdgcn_readfirstlane(lbase + s * SLOT * 8 + k * 1024));
+        if constexpr (CS) return;
 #pragma unroll
         for (int k = 0; k < U / 2; ++k)
             glds16s(cvoff, cb + (int64_t)2 * k * ldc * 8,
                     __builtin_amdgcn_readfirstlane(lbase + s * SLOT * 8 + U * 512 + k * 1024));
+    };
+    // CS: this wave's group of supergroup sg (group G sg + w) into shared slot cs; a group that does not
+    // lie wholly inside the band takes dma's row clamp on the base
+    auto dma_c = [&](int sg, int cs) {
+        const int gq = G * sg + w;
+        const uint32_t dst = cbase + (uint32_t)((cs * G + w) * U * 512);
+        const bool inside = (gq + 1) * U <= nr;   // (uniform)
+        const int gg = gq < ng ? gq : ng - 1;
+#pragma unroll
+        for (int k = 0; k < U / 2; ++k) {
+            const uint32_t m0 = __builtin_amdgcn_readfirstlane(dst + k * 1024);
+            if (inside) {
+                glds16s(cvoff, C + (i0 + gq * U + 2 * k) * ldc, m0);
+            } else {
+                const int rk = gg * U + 2 * k;
+                const bool pair = rk + 1 < nr;
+                glds16s(pair ? cvoff : cvoff & 511u, C + (i0 + (rk < nr ? rk : nr - 1)) * ldc, m0);
+            }
+        }
     };
     // band descriptor (the caller keeps rb * ld * 8 < 2^31): rows at soffset r * ld8; stores
     // of lanes past the width, and of rows with nothing to store, go out of range (dropped)
@@ -1190,12 +1251,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void p
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, v), ro, keep ? voff_st : 0x7fffff00,
                                               (r < nr ? r : 0) * ld8, kSt);
     };
+    if constexpr (CS) dma_c(0, 0);   // (older than group 0's tableau DMAs)
 #pragma unroll
     for (int s = 0; s < D; ++s) dma(s, s);
     int s = 0;
     for (int g = 0; g < ng; ++g) {
-        vmwait_group<D, U>(g);
+        if constexpr (CS) {
+            const int p = g % G;   // the group's place in its supergroup
+            vmwait_group_cs<D, U>(g, p);
+            if (p == 0) {   // (uniform) behind the barrier this supergroup's rows are in, the last one's slot is free
+                asm volatile("s_barrier" ::: "memory");
+                dma_c(g / G + 1, (g / G + 1) % NS);
+            }
+        } else {
+            vmwait_group<D, U>(g);
+        }
         const double* sl = wbase + s * SLOT;
+        // the group's coefficient rows (CS: group g % G of slot g / G % NS)
+        const double* cf = CS ? cring + g % (NS * G) * U * 64 : sl + U * 64;
         const int r0 = g * U;
         // the group's U classes in one LDS read (a short last group is never dense; rb <= 1024)
         const clsv cv = *(const clsv*)(cls + r0);
@@ -1214,7 +1287,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void p
             auto loadc = [&](int h) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    const d2 v = *(const d2*)(sl + U * 64 + u * 64 + h * 32 + 2 * (lane & 15));
+                    const d2 v = *(const d2*)(cf + u * 64 + h * 32 + 2 * (lane & 15));
                     c[u][0] = v.x;
                     c[u][1] = v.y;
                 }
@@ -1228,7 +1301,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void p
                 for (int u = 0; u < U; ++u) {
                     const int cl = __builtin_amdgcn_readfirstlane(cls[r0 + u]) - kDensePiv;
                     if (cl < 0) continue;
-                    const double tp = redo_pivot_row(sl + U * 64 + u * 64, cl, pr);
+                    const double tp = redo_pivot_row(cf + u * 64, cl, pr);
 #pragma unroll
                     for (int k = 0; k < U; ++k) t[k] = k == u ? tp : t[k];
                 }
@@ -1246,7 +1319,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void p
                     store(t, r, outplace && r < nr);
                     continue;
                 }
-                const double* cr = sl + U * 64 + u * 64;   // the row's coefficients (broadcast reads)
+                const double* cr = cf + u * 64;   // the row's coefficients (broadcast reads)
                 t = replay_row(t, cl, pr, [&](int l) { return cr[l]; });
                 store(t, r, true);
             }
@@ -1571,20 +1644,47 @@ constexpr size_t kMfmaLds = kClsLds + 2 * 9 * 128 * sizeof(double);           //
 // a band within one 2 GiB buffer descriptor
 static bool band_in_descriptor(const Geometry& g, int rb) { return (int64_t)rb * g.ld * 8 < ((int64_t)1 << 31); }
 
-// The form-23 instance of (U, D): scalar-base DMAs or per-lane ones (sad), publishing or not (bcnt)
+// DLP_PASS_CSHARE (A/B): 1 / 0: the form-23 pass's coefficient rows fetched once per workgroup (the
+// shared ring, pass_q_kernel's CS) wherever such an instance exists and the scalar-base DMAs are on /
+// nowhere; unset: the shipped choice per geometry (pass_cshare_default)
+static int pass_cshare_env() {
+    static const int v = env_int("DLP_PASS_CSHARE", -1);
+    return v;
+}
+// The shipped choice, by the rows per group (U = 4 from 16,384 local rows, else 2): shared with 4 rows (C3:
+// the pass equal, the chain beside it faster, the bench line +1% in 12 of 12 alternating pairs; c3r2: the
+// pass 2.1% faster), not with 2 (c3r4: the pass 2% slower); DESIGN.md 16.4, profiles/c3_pass_cshare/
+static bool pass_cshare_default(int U) { return U == 4; }
+// The shared ring is compiled for the (U, D) that can be chosen: the two U = 4 depths and U = 2's default
+constexpr bool pass_q_shared_exists(int U, int D) { return (U == 4 && (D == 2 || D == 3)) || (U == 2 && D == 4); }
+constexpr int kCsG = 4, kCsNS = 2;   // pass_q_kernel's G and NS
+// The ring of one form-23 workgroup: 4 waves x D slots of U rows (x 64 columns, and without the shared
+// ring their 64 coefficients), then the shared coefficient ring
+static size_t pass_q_lds(int U, int D, bool shared) {
+    return shared ? ((size_t)4 * D + kCsNS * kCsG) * 64 * U * sizeof(double) : (size_t)4 * D * 128 * U * sizeof(double);
+}
+
+// The form-23 instance of (U, D): scalar-base DMAs or per-lane ones (sad), the shared coefficient ring
+// (csh; with sad), publishing or not (bcnt)
 template <bool NT, int U, int D>
 static void launch_pass_q(const Geometry& g, const Defer& d, const BlockDesc* bd, double* To, int rb,
-                          uint32_t* bcnt, bool sad, int pivg, dim3 grid, size_t dyn, hipStream_t s) {
-    auto go = [&](auto sa, auto pub) {
-        pass_q_kernel<NT, U, D, decltype(sa)::value, decltype(pub)::value><<<grid, 256, dyn, s>>>(
-            g.T, To, g.ld, g.rows, g.width, bd, d.C, d.ldc, d.P, d.nzc, rb, bcnt, pivg);
+                          uint32_t* bcnt, bool sad, bool csh, int pivg, dim3 grid, size_t dyn, hipStream_t s) {
+    auto go = [&](auto sa, auto cs, auto pub) {
+        pass_q_kernel<NT, U, D, decltype(sa)::value, decltype(cs)::value, decltype(pub)::value>
+            <<<grid, 256, dyn, s>>>(g.T, To, g.ld, g.rows, g.width, bd, d.C, d.ldc, d.P, d.nzc, rb, bcnt, pivg);
     };
     constexpr std::true_type yes{};
     constexpr std::false_type no{};
+    if constexpr (pass_q_shared_exists(U, D)) {
+        if (sad && csh) {
+            bcnt ? go(yes, yes, yes) : go(yes, yes, no);
+            return;
+        }
+    }
     if (sad)
-        bcnt ? go(yes, yes) : go(yes, no);
+        bcnt ? go(yes, no, yes) : go(yes, no, no);
     else
-        bcnt ? go(no, yes) : go(no, no);
+        bcnt ? go(no, no, yes) : go(no, no, no);
 }
 
 template <bool NT, int K>
@@ -1667,25 +1767,28 @@ static hipError_t pass(const Geometry& g, const Defer& d, DevState* st, int rb, 
             const bool sad = pass_saddr_env();
             const int U = qu_env == 2 || qu_env == 4 ? qu_env : (g.rows >= 16384 ? 4 : 2);
             const int D = U == 4 ? (qd == 3 ? 3 : 2) : (qd == 2 || qd == 3 || qd == 6 || qd == 8 ? qd : 4);
-            size_t dyn = std::max((size_t)4 * D * 128 * U * sizeof(double), pass_lds_env());
+            // the shared coefficient ring: where DLP_PASS_CSHARE or the shipped choice asks for it
+            const int cse = pass_cshare_env();
+            const bool csh = sad && pass_q_shared_exists(U, D) && (cse >= 0 ? cse != 0 : pass_cshare_default(U));
+            size_t dyn = std::max(pass_q_lds(U, D, csh), pass_lds_env());
             if (occ > 0) dyn = std::max(dyn, occ_lds(occ, kClsLds));
             const dim3 grid((unsigned)((g.width + 255) / 256), nbands);
             if (g.rows <= 0)
                 ;
             else if (U == 4 && D == 3)
-                launch_pass_q<NT, 4, 3>(g, d, bd, To, rb, bcnt, sad, pivg, grid, dyn, s);
+                launch_pass_q<NT, 4, 3>(g, d, bd, To, rb, bcnt, sad, csh, pivg, grid, dyn, s);
             else if (U == 4)
-                launch_pass_q<NT, 4, 2>(g, d, bd, To, rb, bcnt, sad, pivg, grid, dyn, s);
+                launch_pass_q<NT, 4, 2>(g, d, bd, To, rb, bcnt, sad, csh, pivg, grid, dyn, s);
             else if (D == 2)
-                launch_pass_q<NT, 2, 2>(g, d, bd, To, rb, bcnt, sad, pivg, grid, dyn, s);
+                launch_pass_q<NT, 2, 2>(g, d, bd, To, rb, bcnt, sad, csh, pivg, grid, dyn, s);
             else if (D == 3)
-                launch_pass_q<NT, 2, 3>(g, d, bd, To, rb, bcnt, sad, pivg, grid, dyn, s);
+                launch_pass_q<NT, 2, 3>(g, d, bd, To, rb, bcnt, sad, csh, pivg, grid, dyn, s);
             else if (D == 6)
-                launch_pass_q<NT, 2, 6>(g, d, bd, To, rb, bcnt, sad, pivg, grid, dyn, s);
+                launch_pass_q<NT, 2, 6>(g, d, bd, To, rb, bcnt, sad, csh, pivg, grid, dyn, s);
             else if (D == 8)
-                launch_pass_q<NT, 2, 8>(g, d, bd, To, rb, bcnt, sad, pivg, grid, dyn, s);
+                launch_pass_q<NT, 2, 8>(g, d, bd, To, rb, bcnt, sad, csh, pivg, grid, dyn, s);
             else
-                launch_pass_q<NT, 2, 4>(g, d, bd, To, rb, bcnt, sad, pivg, grid, dyn, s);
+                launch_pass_q<NT, 2, 4>(g, d, bd, To, rb, bcnt, sad, csh, pivg, grid, dyn, s);
         }
     } else {
         // streamed forms need K >= 16 (an even number of coefficient chunks): form 3 below
