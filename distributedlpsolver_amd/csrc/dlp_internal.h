@@ -372,6 +372,18 @@ hipError_t launch_dual_row(const Geometry& g, const int32_t* basis, DevState* st
 hipError_t launch_dual_col(const Geometry& g, int32_t* basis, DevState* st, Cand* partials, double tol_piv,
                            int pricing, dlp_pivot* log, int64_t log_cap, hipStream_t s);
 
+// dlp_relayout.hip: the stored tableau between the condensed and the full layout
+// (dlp_session_set_defer).  rows_total: the constraint rows and the objective row.
+// cond_expand: dst (stride ld_d, N variables, RHS at N) from the condensed src (stride ld_s, n slots,
+// RHS at slot n) by the read-out's rule: slot_of[v] >= 0 -> the slot's entry, else 1.0 where v is
+// basis[row], else +0.0; padding +0.0.  cond_pack: the condensed dst (slot s = column var_of[s] of
+// the full src, slot n = column N, padding +0.0).  Values are copied, nothing is computed.
+hipError_t launch_cond_expand(const double* src, int64_t ld_s, int64_t n, double* dst, int64_t ld_d,
+                              int64_t N, int64_t rows_total, const int32_t* slot_of, const int32_t* basis,
+                              hipStream_t s);
+hipError_t launch_cond_pack(const double* src, int64_t ld_s, int64_t N, double* dst, int64_t ld_d, int64_t n,
+                            int64_t rows_total, const int32_t* var_of, hipStream_t s);
+
 // dlp_batched.hip: free the cached dlp_batched_solve contexts of `device` (-1: all); bytes freed
 size_t batched_release(int device);
 

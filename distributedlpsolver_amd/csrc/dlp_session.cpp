@@ -800,6 +800,132 @@ int la_enable(dlp_session* s, bool forced) {
     return DLP_OK;
 }
 
+// ---- the storage plan: K, layout, side arrays ------------------------------
+// One set of rules for session creation and for dlp_session_set_defer, which moves
+// a live session to another (K, layout): both run the functions below.
+
+int64_t row_stride(const dlp_session* s, int64_t width) {
+    const int64_t align = s->opt.ld_align;
+    return (width + align - 1) / align * align;
+}
+
+// a tableau under 32 MiB stays eager: its rank-1 update is a few-µs launch, and
+// the replayed ratio / pivot-row kernels cost more than the passes they save
+// (C4 256x512: 14.2 µs/pivot eager vs 19.0 at K = 16; 1024x1024: 18.0 vs 20.8;
+// C2 4096x8192, 268 MB: K = 16 is 2.3x eager; profiles/r01j/tune_small_defer.txt)
+// (the full layout's size, whatever the session stores)
+bool tiny_tableau(const dlp_session* s) {
+    return (double)(s->rows + 1) * (double)round16(s->N + 1) * 8.0 < (double)(32ll << 20);
+}
+
+// defer = 0 (auto): 64 pivots per tableau pass on a streaming (HBM-resident) tableau through the
+// DPP-coefficient pass (form 21: C3 8.4 ms per 64-step pass = 0.131 ms per step against 0.197 for
+// form 4's 32-step pass, 6,100 vs 4,500 pivots/s; profiles/r02j/), 16 on a cache-resident one, eager
+// on a tiny one, on the small-LP path, and when the chosen rank-1 variant tiles pricing differently
+// from the deferred kernels.  A host-driven rank (the step API) takes the geometry the same rank
+// would run over RCCL, so the multi-GPU split can be exercised without RCCL (general LPs stay eager).
+int auto_defer(const dlp_session* s, bool host_driven, int tile) {
+    return ((host_driven && s->general) || tile != dlp::kDeferTile || tiny_tableau(s) || s->cluster)
+               ? 1
+               : (s->streaming ? 64 : 16);
+}
+
+int defer_tile_check(int K, int tile) {
+    if (K > 1 && tile != dlp::kDeferTile) {
+        set_error("defer > 1 needs a 512-column update variant");
+        return DLP_ERR_ARG;
+    }
+    return DLP_OK;
+}
+
+// pass form 4 (2 doubles x 2 rows per lane; a window's partial last block runs the
+// full-block code with zeroed coefficients: C3 20-pivot partial pass 6.93 ms vs a
+// 6.30 ms full pass, 7.58 for the streamed kernel's (form 14), 12.7 before,
+// profiles/r02c/) at K = 32 on a streaming tableau and K = 16 on a cache-resident one
+// (C2: pass 0.116 vs 0.128 ms for form 3, profiles/r02b/tune_c2_forms.txt); 1 double
+// x 4 rows elsewhere (K = 16 streaming: form 3 6.1 ms vs form 4 6.4, r01g)
+int defer_form_rule(const dlp_session* s, int K) {
+    return (K == 64 && s->streaming) ? 21 : ((K == 32 && s->streaming) || (K == 16 && !s->streaming)) ? 4 : 3;
+}
+
+// condensed tableau: a deferred session of a dense / random /
+// ad-allocation LP stores only the n nonbasic columns + the RHS (the m basic columns are
+// unit vectors); the size-based policies keep the full tableau's scale
+bool condensed_rule(const dlp_session* s, int creq, int K) {
+    return (creq == 1 || (creq == 0 && condensed_auto())) && K > 1 && !s->general && !s->cluster;
+}
+
+// The stored layout's dimensions (cond: the condensed one): width, row stride, the RHS column and
+// the priced columns, the update kernel's tiles.  ld_full: the stride of the full layout, which the
+// read-outs of a condensed session keep.
+void set_layout(dlp_session* s, bool cond) {
+    const int tile = dlp::update_tile(s->opt.update_variant);
+    s->ld_full = row_stride(s, round16(s->N + 1));
+    s->width = round16((cond ? s->n : s->N) + 1);
+    s->ld = row_stride(s, s->width);
+    s->g.cd.on = cond ? 1 : 0;
+    s->g.ld = s->ld;
+    s->g.width = s->width;
+    s->g.ncols = cond ? s->n : s->N;
+    s->g.nprice = cond ? s->n : s->nprice;
+    s->g.ntiles = (int)((s->width + tile - 1) / tile);
+}
+
+// The selection launches' sizes for the geometry and K: ratio workgroups (the partials' capacity),
+// whether the fused pivot's grid is resident at once.
+void plan_side(dlp_session* s) {
+    s->ratio_blocks = dlp::ratio_blocks(s->g);
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device) != hipSuccess)
+        cus = 0;
+    // (the kernel's real occupancy, not an assumed 2 per CU: ADVICE r02)
+    s->fuse_fits = s->d.K > 1 && s->d.K <= 32 &&
+                   dlp::fused_pivot_blocks(s->g) <= std::min(2 * cus, dlp::fused_pivot_capacity(s->d.K, cus));
+    s->ratio_blocks_max = std::max(s->ratio_blocks, dlp::ratio_defer_blocks(s->g));
+}
+
+// The slot maps of a condensed layout (sized by N and the stride).
+int alloc_cond_maps(dlp_session* s) {
+    HIP_TRY(pool_alloc(s, s->device, (void**)&s->g.cd.slot_of, sizeof(int32_t) * s->N));
+    HIP_TRY(pool_alloc(s, s->device, (void**)&s->g.cd.var_of, sizeof(int32_t) * s->ld));
+    HIP_TRY(pool_alloc(s, s->device, (void**)&s->g.cd.rst, sizeof(int32_t) * s->ld));
+    return DLP_OK;
+}
+
+// The arrays sized by the row stride: the pivot-row exchange buffers (zeroed) and the pricing
+// partials.
+int alloc_stride_arrays(dlp_session* s) {
+    HIP_TRY(pool_alloc(s, s->device, (void**)&s->prow_send, sizeof(int64_t) * s->ld));
+    if (s->exchange)
+        HIP_TRY(pool_alloc(s, s->device, (void**)&s->prow_recv, sizeof(int64_t) * s->ld));
+    else
+        s->prow_recv = s->prow_send;
+    HIP_TRY(pool_alloc(s, s->device, (void**)&s->pp, sizeof(dlp::PricePart) * ((s->ld + 511) / 512)));
+    HIP_TRY(hipMemsetAsync(s->prow_send, 0, sizeof(int64_t) * s->ld, s->stream));
+    return DLP_OK;
+}
+
+// The block arrays of a deferred path (s->d.K > 1), an empty block in them, and the pass band.
+int alloc_defer_arrays(dlp_session* s) {
+    const int64_t rows_total = s->rows + 1;
+    s->d.ldc = s->d.K;
+    HIP_TRY(pool_alloc(s, s->device, (void**)&s->d.C, sizeof(double) * s->d.K * (rows_total + 1)));
+    s->d.ldcc = (rows_total + 1 + 63) / 64 * 64;
+    HIP_TRY(pool_alloc(s, s->device, (void**)&s->d.Cc, sizeof(double) * s->d.K * s->d.ldcc));
+    HIP_TRY(hipMemsetAsync(s->d.Cc, 0, sizeof(double) * s->d.K * s->d.ldcc, s->stream));
+    // P is sized for the pass template's block (K rounded up to 4/8/16/32/64), so a
+    // kernel instance never addresses past it, whatever the session's K
+    const int64_t kt = s->d.K <= 4 ? 4 : s->d.K <= 8 ? 8 : s->d.K <= 16 ? 16 : s->d.K <= 32 ? 32 : 64;
+    HIP_TRY(pool_alloc(s, s->device, (void**)&s->d.P, sizeof(double) * kt * s->ld));
+    HIP_TRY(pool_alloc(s, s->device, (void**)&s->d.rhs, sizeof(double) * (s->rows + 1)));
+    HIP_TRY(pool_alloc(s, s->device, (void**)&s->d.nzc, sizeof(int32_t) * (s->rows + 1)));
+    HIP_TRY(hipMemsetAsync(s->d.C, 0, sizeof(double) * s->d.K * (rows_total + 1), s->stream));
+    HIP_TRY(hipMemsetAsync(s->d.P, 0, sizeof(double) * kt * s->ld, s->stream));
+    s->defer_rb_req = s->opt.rows_per_block > 0 ? s->opt.rows_per_block : 0;
+    s->defer_rb = s->defer_rb_req > 0 ? fit_defer_rb(s, s->defer_rb_req) : auto_defer_rb(s);
+    return DLP_OK;
+}
+
 // comm_in: a communicator made by the caller (dlp_solve's in-process multi-device
 // path, ncclCommInitAll); the session then owns it.  uid: a unique id shared by
 // P processes (ncclCommInitRank here).  Either one means the RCCL exchange.
@@ -853,7 +979,7 @@ int session_init(const dlp_problem* prob, const dlp_options* opt, int rank, int 
         set_error("ld_align must be a multiple of 16 doubles");
         return DLP_ERR_ARG;
     }
-    s->ld = (s->width + align - 1) / align * align;
+    s->ld = row_stride(s, s->width);
     opt = &s->opt;
     s->prob_dims.m = prob->m;
     s->prob_dims.n = prob->n;
@@ -884,12 +1010,8 @@ int session_init(const dlp_problem* prob, const dlp_options* opt, int rank, int 
 
     const int64_t rows_total = s->rows + 1;
     dlp::Geometry& g = s->g;
-    g.ld = s->ld;
-    g.width = s->width;
     g.rows = s->rows;
     g.row_first = s->row_first;
-    g.ncols = s->N;
-    g.nprice = s->nprice;
     g.rows_elig = rows_elig;
     g.rthreads = ratio_threads_policy(s);
     if (opt->update_variant < 0 || opt->update_variant >= dlp::update_variants()) {
@@ -897,11 +1019,10 @@ int session_init(const dlp_problem* prob, const dlp_options* opt, int rank, int 
         return DLP_ERR_ARG;
     }
     const int tile = dlp::update_tile(opt->update_variant);
-    g.ntiles = (int)((s->width + tile - 1) / tile);
-    // deferred rank-k update: auto = 32 pivots per tableau pass on a streaming
-    // (HBM-resident) tableau, 16 on a cache-resident one, eager on a tiny one; eager when the
-    // caller drives the exchange itself (dlp_session_step_*) or when the chosen
-    // rank-1 variant tiles pricing differently from the deferred kernels
+    set_layout(s, false);
+    // deferred rank-k update: auto_defer's size rule; eager when the caller drives the exchange
+    // itself (dlp_session_step_*) or when the chosen rank-1 variant tiles pricing differently
+    // from the deferred kernels
     {
         const bool host_driven = nranks > 1 && !rccl;
         int K = opt->defer;
@@ -909,11 +1030,7 @@ int session_init(const dlp_problem* prob, const dlp_options* opt, int rank, int 
             set_error("defer must be 0 (auto) or 1..64");
             return DLP_ERR_ARG;
         }
-        // a tableau under 32 MiB stays eager: its rank-1 update is a few-µs launch, and
-        // the replayed ratio / pivot-row kernels cost more than the passes they save
-        // (C4 256x512: 14.2 µs/pivot eager vs 19.0 at K = 16; 1024x1024: 18.0 vs 20.8;
-        // C2 4096x8192, 268 MB: K = 16 is 2.3x eager; profiles/r01j/tune_small_defer.txt)
-        const bool tiny = (double)(s->rows + 1) * (double)s->width * 8.0 < (double)(32ll << 20);
+        const bool tiny = tiny_tableau(s);
         // small LPs (auto: tiny, default kernels; or forced by small_lp = 1): one launch per
         // window with the tableau in LDS, when it fits the CUs' LDS (dlp_cluster.hip)
         int cus = 0;
@@ -933,62 +1050,27 @@ int session_init(const dlp_problem* prob, const dlp_options* opt, int rank, int 
             }
             s->cluster = s->cl_wg > 0;
         }
-        // streaming tableaus: 64-step blocks through the DPP-coefficient pass (form 21: C3
-        // 8.4 ms per 64-step pass = 0.131 ms per step against 0.197 for form 4's 32-step
-        // pass, 6,100 vs 4,500 pivots/s; profiles/r02j/)
-        // a host-driven rank (the step API) takes the geometry the same rank would run over
-        // RCCL, so the multi-GPU split can be exercised without RCCL (general LPs stay eager)
-        if (K == 0)
-            K = ((host_driven && s->general) || tile != dlp::kDeferTile || tiny || s->cluster)
-                    ? 1
-                    : (s->streaming ? 64 : 16);
+        if (K == 0) K = auto_defer(s, host_driven, tile);
         if (s->cluster && K != 1) s->cluster = false;
-        if (K > 1 && tile != dlp::kDeferTile) {
-            set_error("defer > 1 needs a 512-column update variant");
-            return DLP_ERR_ARG;
-        }
+        CALL_TRY(defer_tile_check(K, tile));
         if (K > 1 && host_driven && s->general) {
             set_error("a host-driven (step API) general-LP session is eager: create it with defer = 1");
             return DLP_ERR_ARG;
         }
         s->d.K = K;
         s->opt.defer = K;
-        // pass form 4 (2 doubles x 2 rows per lane; a window's partial last block runs the
-        // full-block code with zeroed coefficients: C3 20-pivot partial pass 6.93 ms vs a
-        // 6.30 ms full pass, 7.58 for the streamed kernel's (form 14), 12.7 before,
-        // profiles/r02c/) at K = 32 on a streaming tableau and K = 16 on a cache-resident one
-        // (C2: pass 0.116 vs 0.128 ms for form 3, profiles/r02b/tune_c2_forms.txt); 1 double
-        // x 4 rows elsewhere (K = 16 streaming: form 3 6.1 ms vs form 4 6.4, r01g)
-        s->d.form = (K == 64 && s->streaming) ? 21
-                    : ((K == 32 && s->streaming) || (K == 16 && !s->streaming)) ? 4 : 3;
-        // condensed tableau: a deferred session of a dense / random /
-        // ad-allocation LP stores only the n nonbasic columns + the RHS (the m basic columns are
-        // unit vectors); the size-based policies above keep the full tableau's scale
+        s->d.form = defer_form_rule(s, K);
         const int creq = opt->condensed;
         if (creq < -1 || creq > 1) {
             set_error("condensed must be -1 (off), 0 (auto) or 1 (on)");
             return DLP_ERR_ARG;
         }
-        if ((creq == 1 || (creq == 0 && condensed_auto())) && K > 1 && !s->general && !s->cluster) {
-            s->g.cd.on = 1;
-            s->ld_full = s->ld;   // (the read-outs keep the full layout's stride)
-            s->width = round16(s->n + 1);
-            s->ld = (s->width + align - 1) / align * align;
-            g.ld = s->ld;
-            g.width = s->width;
-            g.ncols = s->n;
-            g.nprice = s->n;
-            g.ntiles = (int)((s->width + tile - 1) / tile);
-        }
+        if (condensed_rule(s, creq, K)) set_layout(s, true);   // (the read-outs keep the full layout's stride)
     }
     g.rows_per_block = opt->rows_per_block > 0 ? opt->rows_per_block : auto_rows_per_block(s);
     g.rows_per_block = std::min(g.rows_per_block, dlp::kMaxBandLdsHost);
     const size_t tbytes = (size_t)rows_total * s->ld * sizeof(double);
-    if (s->g.cd.on) {
-        HIP_TRY(pool_alloc(s, s->device, (void**)&s->g.cd.slot_of, sizeof(int32_t) * s->N));
-        HIP_TRY(pool_alloc(s, s->device, (void**)&s->g.cd.var_of, sizeof(int32_t) * s->ld));
-        HIP_TRY(pool_alloc(s, s->device, (void**)&s->g.cd.rst, sizeof(int32_t) * s->ld));
-    }
+    if (s->g.cd.on) CALL_TRY(alloc_cond_maps(s));
     if (pool_alloc(s, s->device, (void**)&s->T, tbytes) != hipSuccess) {
         set_error("hipMalloc of the tableau failed (" + std::to_string(tbytes) + " bytes)");
         return DLP_ERR_OOM;
@@ -998,51 +1080,20 @@ int session_init(const dlp_problem* prob, const dlp_options* opt, int rank, int 
     if (s->cluster) {
         HIP_TRY(pool_alloc(s, s->device, (void**)&s->cl_gran, sizeof(uint64_t) * dlp::cluster_granules(s->m, s->cl_wg)));
     }
-    s->ratio_blocks = dlp::ratio_blocks(g);
-    {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device) != hipSuccess)
-            cus = 0;
-        // (the kernel's real occupancy, not an assumed 2 per CU: ADVICE r02)
-        s->fuse_fits = s->d.K > 1 && s->d.K <= 32 &&
-                       dlp::fused_pivot_blocks(g) <= std::min(2 * cus, dlp::fused_pivot_capacity(s->d.K, cus));
-    }
-    s->ratio_blocks_max = std::max(s->ratio_blocks, dlp::ratio_defer_blocks(g));
+    plan_side(s);
     HIP_TRY(pool_alloc(s, s->device, (void**)&s->colq, sizeof(double) * (rows_total + dlp::kColqPad)));
     HIP_TRY(hipMemsetAsync(s->colq, 0, sizeof(double) * (rows_total + dlp::kColqPad), s->stream));
     s->exchange = nranks > 1 || rccl;
-    HIP_TRY(pool_alloc(s, s->device, (void**)&s->prow_send, sizeof(int64_t) * s->ld));
-    if (s->exchange)
-        HIP_TRY(pool_alloc(s, s->device, (void**)&s->prow_recv, sizeof(int64_t) * s->ld));
-    else
-        s->prow_recv = s->prow_send;
+    CALL_TRY(alloc_stride_arrays(s));
     HIP_TRY(pool_alloc(s, s->device, (void**)&s->partials, sizeof(dlp::Cand) * s->ratio_blocks_max));
     HIP_TRY(pool_alloc(s, s->device, (void**)&s->cand_send, sizeof(dlp::Cand)));
     HIP_TRY(pool_alloc(s, s->device, (void**)&s->cand_recv, sizeof(dlp::Cand) * nranks));
-    HIP_TRY(pool_alloc(s, s->device, (void**)&s->pp, sizeof(dlp::PricePart) * ((s->ld + 511) / 512)));
     HIP_TRY(pool_alloc(s, s->device, (void**)&s->basis, sizeof(int32_t) * s->m));
     HIP_TRY(pool_alloc(s, s->device, (void**)&s->st, sizeof(dlp::DevState)));
     s->log_cap = opt->log_pivots ? std::max<int64_t>(1, opt->max_pivots) : 0;
     if (s->log_cap > 0) HIP_TRY(pool_alloc(s, s->device, (void**)&s->log, sizeof(dlp_pivot) * s->log_cap));
     HIP_TRY(pool_alloc(s, -1, (void**)&s->host_st, sizeof(dlp::DevState)));
-    if (s->d.K > 1) {
-        s->d.ldc = s->d.K;
-        HIP_TRY(pool_alloc(s, s->device, (void**)&s->d.C, sizeof(double) * s->d.K * (rows_total + 1)));
-        s->d.ldcc = (rows_total + 1 + 63) / 64 * 64;
-        HIP_TRY(pool_alloc(s, s->device, (void**)&s->d.Cc, sizeof(double) * s->d.K * s->d.ldcc));
-        HIP_TRY(hipMemsetAsync(s->d.Cc, 0, sizeof(double) * s->d.K * s->d.ldcc, s->stream));
-        // P is sized for the pass template's block (K rounded up to 4/8/16/32/64), so a
-        // kernel instance never addresses past it, whatever the session's K
-        const int64_t kt = s->d.K <= 4 ? 4 : s->d.K <= 8 ? 8 : s->d.K <= 16 ? 16 : s->d.K <= 32 ? 32 : 64;
-        HIP_TRY(pool_alloc(s, s->device, (void**)&s->d.P, sizeof(double) * kt * s->ld));
-        HIP_TRY(pool_alloc(s, s->device, (void**)&s->d.rhs, sizeof(double) * (s->rows + 1)));
-        HIP_TRY(pool_alloc(s, s->device, (void**)&s->d.nzc, sizeof(int32_t) * (s->rows + 1)));
-        HIP_TRY(hipMemsetAsync(s->d.C, 0, sizeof(double) * s->d.K * (rows_total + 1), s->stream));
-        HIP_TRY(hipMemsetAsync(s->d.P, 0, sizeof(double) * kt * s->ld, s->stream));
-        s->defer_rb_req = opt->rows_per_block > 0 ? opt->rows_per_block : 0;
-        s->defer_rb = s->defer_rb_req > 0 ? fit_defer_rb(s, s->defer_rb_req) : auto_defer_rb(s);
-    }
-    HIP_TRY(hipMemsetAsync(s->prow_send, 0, sizeof(int64_t) * s->ld, s->stream));
+    if (s->d.K > 1) CALL_TRY(alloc_defer_arrays(s));
     clk.mark("create: side arrays");
 
     // tableau
@@ -1228,6 +1279,15 @@ int la_block_end(dlp_session* s, bool drain, hipEvent_t* evp) {
 
 // Back to the single-buffer path (step API, a pass form without an out-of-place
 // instance): finish what is in flight; slot 0's arrays serve the in-place blocks.
+// (the teardown alone, on a drained and synchronised session: dlp_session_set_defer runs it after
+// flush_pending, once its new buffers are allocated)
+int la_teardown(dlp_session* s) {
+    s->la = false;
+    s->opt.lookahead = 0;
+    CALL_TRY(chain_cus_apply(s, 0));   // the pass runs on the chain's stream again: every CU
+    return DLP_OK;
+}
+
 int la_disable(dlp_session* s) {
     if (!s->la) return DLP_OK;
     if (s->since_flush > 0) CALL_TRY(la_block_end(s, true, nullptr));
@@ -1236,9 +1296,7 @@ int la_disable(dlp_session* s) {
     const int form = s->d.form;
     s->d = s->dslot[0];
     s->d.form = form;
-    s->la = false;
-    s->opt.lookahead = 0;
-    CALL_TRY(chain_cus_apply(s, 0));   // the pass runs on the chain's stream again: every CU
+    CALL_TRY(la_teardown(s));
     pick_form(s);
     return DLP_OK;
 }
@@ -2427,6 +2485,63 @@ int sessions_phase(dlp_session* const* ss, int P, int phase, int64_t slot, bool 
 }  // namespace
 
 // =========================================================================
+// dlp_session_set_defer: what the switch replaces, saved so that a failed allocation restores it
+namespace {
+struct StoreState {   // what the switch replaces
+    int64_t width, ld, ld_full;
+    dlp::Geometry g;
+    double* T;
+    int64_t *prow_send, *prow_recv;
+    dlp::PricePart* pp;
+    dlp::Cand* partials;
+    int ratio_blocks, ratio_blocks_max;
+    dlp::Defer d;
+    bool fuse_fits;
+    int defer_rb, defer_rb_req, opt_defer;
+};
+StoreState store_save(const dlp_session* s) {
+    return {s->width, s->ld, s->ld_full, s->g, s->T, s->prow_send, s->prow_recv, s->pp, s->partials,
+            s->ratio_blocks, s->ratio_blocks_max, s->d, s->fuse_fits, s->defer_rb, s->defer_rb_req, s->opt.defer};
+}
+// Back to `o`, the buffers allocated since released.
+void store_restore(dlp_session* s, const StoreState& o) {
+    void* fresh[] = {s->T != o.T ? s->T : nullptr,
+                     s->prow_send != o.prow_send ? s->prow_send : nullptr,
+                     s->pp != o.pp ? s->pp : nullptr,
+                     s->partials != o.partials ? s->partials : nullptr,
+                     s->g.cd.slot_of != o.g.cd.slot_of ? s->g.cd.slot_of : nullptr,
+                     s->g.cd.var_of != o.g.cd.var_of ? s->g.cd.var_of : nullptr,
+                     s->g.cd.rst != o.g.cd.rst ? s->g.cd.rst : nullptr,
+                     s->d.C != o.d.C ? s->d.C : nullptr,
+                     s->d.Cc != o.d.Cc ? s->d.Cc : nullptr,
+                     s->d.P != o.d.P ? s->d.P : nullptr,
+                     s->d.rhs != o.d.rhs ? s->d.rhs : nullptr,
+                     s->d.nzc != o.d.nzc ? s->d.nzc : nullptr};
+    (void)hipStreamSynchronize(s->stream);   // (their memsets)
+    for (void* p : fresh) pool_release(s, s->device, p);
+    s->width = o.width;
+    s->ld = o.ld;
+    s->ld_full = o.ld_full;
+    s->g = o.g;
+    s->T = o.T;
+    s->prow_send = o.prow_send;
+    s->prow_recv = o.prow_recv;
+    s->pp = o.pp;
+    s->partials = o.partials;
+    s->ratio_blocks = o.ratio_blocks;
+    s->ratio_blocks_max = o.ratio_blocks_max;
+    s->d = o.d;
+    s->fuse_fits = o.fuse_fits;
+    s->defer_rb = o.defer_rb;
+    s->defer_rb_req = o.defer_rb_req;
+    s->opt.defer = o.opt_defer;
+}
+void drop_graph(dlp_session* s) {
+    if (s->gexec) { (void)hipGraphExecDestroy(s->gexec); s->gexec = nullptr; }
+    if (s->graph) { (void)hipGraphDestroy(s->graph); s->graph = nullptr; }
+}
+}  // namespace
+
 extern "C" {
 
 void dlp_options_default(dlp_options* o) {
@@ -2967,10 +3082,12 @@ int dlp_session_set_objective(dlp_session* s, const double* c, int64_t n, double
         HIP_TRY(pool_alloc(s, s->device, (void**)&s->ro_rows, sizeof(int32_t) * std::max<int64_t>(s->m, 1)));
         HIP_TRY(pool_alloc(s, s->device, (void**)&s->ro_cb, sizeof(double) * std::max<int64_t>(s->m, 1)));
         HIP_TRY(pool_alloc(s, s->device, (void**)&s->ro_c, sizeof(double) * std::max<int64_t>(s->n, 1)));
-        if (!s->g.cd.on) HIP_TRY(pool_alloc(s, s->device, (void**)&s->ro_basic, sizeof(int32_t) * s->width));
         HIP_TRY(hipEventCreate(&s->ro_ev[0]));
         HIP_TRY(hipEventCreate(&s->ro_ev[1]));
     }
+    // (on its own: dlp_session_set_defer frees it with the full layout it belongs to)
+    if (!s->g.cd.on && !s->ro_basic)
+        HIP_TRY(pool_alloc(s, s->device, (void**)&s->ro_basic, sizeof(int32_t) * s->width));
     // a deferred block in progress applied, a lookahead pass drained: T and the objective row
     // both in s->T, every column of it current
     CALL_TRY(flush_pending(s));
@@ -3050,7 +3167,8 @@ int dlp_session_set_rhs(dlp_session* s, const double* b, int64_t m, double* kern
     if (s->d.K > 1 || s->la || s->g.cd.on) {
         set_error("dlp_session_set_rhs: a deferred session (defer = " + std::to_string(s->d.K) +
                   ") is not supported: its replay state and RHS cache would have to be re-established "
-                  "after the eager dual pivots; create the session with defer = 1");
+                  "after the eager dual pivots; create the session with defer = 1 or call "
+                  "dlp_session_set_defer(s, 1, ...) first");
         return DLP_ERR_UNSUPPORTED;
     }
     if (s->status < 0) {
@@ -3106,6 +3224,238 @@ int dlp_session_set_rhs(dlp_session* s, const double* b, int64_t m, double* kern
     // the pivot budget counts pivots: launches enqueued after the previous optimum did none
     s->launched = s->npivots;
     s->dual = true;
+    return DLP_OK;
+}
+
+// Storage switch of a live session: another K, another layout, lookahead on or off,
+// between runs.  Everything is validated first; then the pending block is applied and the lookahead
+// drained (neither is observable), the new buffers are allocated (a failure releases them and
+// returns with the session on its old path), the tableau is moved by dlp_relayout.hip when the
+// layout changes, and the state creation would have set for the new path is set: an empty block,
+// fresh slot maps, pricing partials, the RHS cache, the lookahead.
+int dlp_session_set_defer(dlp_session* s, int defer, int condensed, int lookahead, double* kernel_ms) {
+    if (!s) {
+        set_error("dlp_session_set_defer: session is NULL");
+        return DLP_ERR_ARG;
+    }
+    if (defer < 0 || defer > dlp::kMaxDefer) {
+        set_error("defer must be 0 (auto) or 1..64");
+        return DLP_ERR_ARG;
+    }
+    if (condensed < -1 || condensed > 1) {
+        set_error("condensed must be -1 (off), 0 (auto) or 1 (on)");
+        return DLP_ERR_ARG;
+    }
+    if (lookahead < -1 || lookahead > 1) {
+        set_error("lookahead must be -1 (auto), 0 (off) or 1 (on)");
+        return DLP_ERR_ARG;
+    }
+    const int tile = dlp::update_tile(s->opt.update_variant);
+    CALL_TRY(defer_tile_check(defer, tile));
+    if (s->general) {
+        set_error("dlp_session_set_defer: general / MPS problems are not supported (their Phase I -> II "
+                  "switch runs on the eager full layout)");
+        return DLP_ERR_UNSUPPORTED;
+    }
+    if (s->nranks > 1 || s->exchange) {
+        set_error("dlp_session_set_defer: single-GPU sessions only (every rank of a row-block session "
+                  "would have to switch at the same point of the exchange)");
+        return DLP_ERR_UNSUPPORTED;
+    }
+    if (s->cluster) {
+        set_error("dlp_session_set_defer: a session on the one-launch small-LP path is not supported "
+                  "(its tableau lives in LDS during a window)");
+        return DLP_ERR_UNSUPPORTED;
+    }
+    if (s->status < 0) {
+        set_error("dlp_session_set_defer: the session has failed");
+        return DLP_ERR_STATE;
+    }
+    if (s->step_open) {
+        set_error("dlp_session_set_defer: a caller-driven step is in progress (finish it with "
+                  "dlp_session_step_update)");
+        return DLP_ERR_STATE;
+    }
+    if (dual_pending(s)) {
+        set_error("dlp_session_set_defer: a dual phase is pending or ended infeasible (the right-hand side "
+                  "has negative entries, which no deferred primal path may see): finish it with "
+                  "dlp_session_run or call dlp_session_set_rhs");
+        return DLP_ERR_STATE;
+    }
+    // the target path, by creation's rules
+    const int K = defer == 0 ? auto_defer(s, false, tile) : defer;
+    const bool cond = condensed_rule(s, condensed, K);
+    const bool la_want = K > 1 && (lookahead == 1 || (lookahead < 0 && K == 64 && s->streaming));
+    if (kernel_ms) *kernel_ms = 0.0;
+    const bool relayout = cond != (s->g.cd.on != 0);
+    if (!relayout && K == s->d.K && la_want == s->la) return DLP_OK;   // the path it runs: nothing touched
+    HIP_TRY(hipSetDevice(s->device));
+    if (!relayout && K == s->d.K) {   // the lookahead alone, as between the runs of any session
+        CALL_TRY(la_want ? la_enable(s, lookahead == 1) : la_disable(s));
+        s->la_auto = lookahead < 0;
+        s->opt.lookahead = s->la ? 1 : 0;
+        pick_form(s);
+        drop_graph(s);
+        return DLP_OK;
+    }
+    // a partial block applied, a lookahead pass drained: every column of s->T current
+    CALL_TRY(flush_pending(s));
+    std::vector<int32_t> basis(s->m);
+    HIP_TRY(hipMemcpyAsync(basis.data(), s->basis, sizeof(int32_t) * s->m, hipMemcpyDeviceToHost, s->stream));
+    CALL_TRY(poll(s));   // (synchronises the stream; npivots and status as the device has them)
+    if (s->status < 0) {
+        set_error("dlp_session_set_defer: the session has failed");
+        return DLP_ERR_STATE;
+    }
+
+    // ---- the new plan and its buffers, beside the old ones
+    const StoreState old = store_save(s);
+    const int64_t rows_total = s->rows + 1;
+    s->d = dlp::Defer{};
+    s->d.K = K;
+    s->opt.defer = K;
+    s->d.form = defer_form_rule(s, K);
+    if (relayout) {
+        s->T = nullptr;
+        s->prow_send = s->prow_recv = nullptr;
+        s->pp = nullptr;
+        s->g.cd = dlp::Cond{};
+        set_layout(s, cond);
+    }
+    plan_side(s);
+    int rc = DLP_OK;
+    if (relayout) {
+        if (cond) rc = alloc_cond_maps(s);
+        if (rc == DLP_OK &&
+            pool_alloc(s, s->device, (void**)&s->T, (size_t)rows_total * s->ld * sizeof(double)) != hipSuccess)
+            rc = DLP_ERR_OOM;
+        s->g.T = s->T;
+        if (rc == DLP_OK) rc = alloc_stride_arrays(s);
+    }
+    if (rc == DLP_OK && s->ratio_blocks_max > old.ratio_blocks_max) {
+        s->partials = nullptr;
+        if (pool_alloc(s, s->device, (void**)&s->partials, sizeof(dlp::Cand) * s->ratio_blocks_max) != hipSuccess)
+            rc = DLP_ERR_OOM;
+    } else {
+        s->ratio_blocks_max = std::max(s->ratio_blocks_max, old.ratio_blocks_max);   // (the capacity)
+    }
+    if (rc == DLP_OK && K > 1) rc = alloc_defer_arrays(s);
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (rc == DLP_OK && relayout &&
+        (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess))
+        rc = DLP_ERR_HIP;
+    if (rc != DLP_OK) {
+        (void)hipGetLastError();
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        store_restore(s, old);
+        set_error("dlp_session_set_defer: the buffers of the new path do not fit beside the old ones");
+        return DLP_ERR_OOM;
+    }
+
+    // ---- the switch
+    if (s->la) CALL_TRY(la_teardown(s));
+    // the slot maps of a condensed target: the nonbasic variables ascending in slots 0..n-1, no
+    // restart (a condensed layout that stays keeps its slots and forgets its restarts: every
+    // block they refer to has been applied)
+    std::vector<int32_t> slot_of, var_of;
+    if (relayout && cond) {
+        slot_of.assign(s->N, 0);
+        var_of.assign(s->ld, -1);
+        for (int64_t i = 0; i < s->m; ++i)
+            if (basis[i] >= 0 && basis[i] < s->N) slot_of[basis[i]] = -1;
+        int32_t next = 0;
+        for (int64_t v = 0; v < s->N; ++v)
+            if (slot_of[v] == 0 && next < s->n) {
+                slot_of[v] = next;
+                var_of[next++] = (int32_t)v;
+            } else {
+                slot_of[v] = -1;
+            }
+        HIP_TRY(hipMemcpyAsync(s->g.cd.slot_of, slot_of.data(), sizeof(int32_t) * s->N, hipMemcpyHostToDevice,
+                               s->stream));
+        HIP_TRY(hipMemcpyAsync(s->g.cd.var_of, var_of.data(), sizeof(int32_t) * s->ld, hipMemcpyHostToDevice,
+                               s->stream));
+    }
+    if (cond) HIP_TRY(hipMemsetAsync(s->g.cd.rst, 0xff, sizeof(int32_t) * s->ld, s->stream));
+    if (relayout) {
+        HIP_TRY(hipEventRecord(ev[0], s->stream));
+        if (cond)
+            HIP_TRY(dlp::launch_cond_pack(old.T, old.ld, s->N, s->T, s->ld, s->n, rows_total, s->g.cd.var_of,
+                                          s->stream));
+        else
+            HIP_TRY(dlp::launch_cond_expand(old.T, old.ld, s->n, s->T, s->ld, s->N, rows_total, old.g.cd.slot_of,
+                                            s->basis, s->stream));
+        HIP_TRY(hipEventRecord(ev[1], s->stream));
+    }
+    if (K > 1) {   // an empty block, as creation leaves it (host_st: the device's state, read by poll)
+        dlp::DevState* h = s->host_st;
+        h->blk = 0;
+        for (int l = 0; l < dlp::kMaxDefer; ++l) h->pl[l] = -1;
+        h->sq = -1;
+        h->bser = 0;
+        for (auto& sl : h->seal) {
+            sl.blk = 0;
+            sl.ser = -1;
+        }
+        HIP_TRY(hipMemcpyAsync(s->st, h, sizeof(dlp::DevState), hipMemcpyHostToDevice, s->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));   // the old buffers are no longer read
+    if (relayout && kernel_ms) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        *kernel_ms = ms;
+    }
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+
+    // ---- the old path's buffers back to the pool
+    {
+        double* other = s->Tb[0] == old.T ? s->Tb[1] : s->Tb[0];   // the lookahead's second buffer
+        void* gone[] = {other,
+                        relayout ? old.T : nullptr,
+                        relayout ? old.prow_send : nullptr,
+                        relayout ? old.pp : nullptr,
+                        relayout ? old.g.cd.slot_of : nullptr,
+                        relayout ? old.g.cd.var_of : nullptr,
+                        relayout ? old.g.cd.rst : nullptr,
+                        s->partials != old.partials ? old.partials : nullptr,
+                        old.d.C, old.d.Cc, old.d.P, old.d.rhs, old.d.nzc,
+                        s->dslot[1].C != old.d.C ? s->dslot[1].C : nullptr,
+                        s->dslot[1].C != old.d.C ? s->dslot[1].Cc : nullptr,
+                        s->dslot[1].C != old.d.C ? s->dslot[1].P : nullptr,
+                        s->dslot[1].C != old.d.C ? s->dslot[1].nzc : nullptr,
+                        s->band_cnt,
+                        relayout ? s->du_part : nullptr,
+                        cond ? s->ro_basic : nullptr};
+        for (void* p : gone) pool_release(s, s->device, p);
+        s->Tb[0] = s->T;
+        s->Tb[1] = nullptr;
+        s->dslot[0] = s->dslot[1] = dlp::Defer{};
+        s->band_cnt = nullptr;
+        s->band_stride = 0;
+        if (relayout) s->du_part = nullptr;
+        if (cond) s->ro_basic = nullptr;
+    }
+    s->tread = s->tcur = s->zbuf = s->cur = 0;
+    s->la_pending = false;
+    s->since_flush = 0;
+    s->ev_pending = 0;
+    s->fuse_pivot = false;   // off as at creation
+    s->form_auto = true;     // creation's form for the new K (dlp_session_set_defer_tuning overrides)
+    s->opt.condensed = condensed;
+    drop_graph(s);           // windows captured on the old geometry
+    s->graph_chunk = 0;
+
+    // ---- what creation derives from the tableau: pricing partials, the RHS cache, the lookahead
+    HIP_TRY(dlp::launch_price_init(s->g, s->pp, s->opt.tol_dj, s->opt.update_variant, s->stream));
+    if (K > 1 && s->rows > 0)
+        HIP_TRY(dlp::launch_gather_column(s->T, s->ld, s->rows, s->g.ncols, s->d.rhs, s->stream));
+    s->la_auto = lookahead < 0;
+    if (la_want) CALL_TRY(la_enable(s, lookahead == 1));
+    s->opt.lookahead = s->la ? 1 : 0;
+    pick_form(s);
+    HIP_TRY(hipStreamSynchronize(s->stream));
     return DLP_OK;
 }
 
@@ -3181,6 +3531,7 @@ int dlp_session_set_tuning(dlp_session* s, int update_variant, int rows_per_bloc
     }
     s->opt.update_variant = update_variant;
     s->opt.nontemporal = nontemporal;
+    s->opt.rows_per_block = rows_per_block;   // the request: a later dlp_session_set_defer keeps it
     const int tile = dlp::update_tile(update_variant);
     s->g.ntiles = (int)((s->width + tile - 1) / tile);
     s->g.rows_per_block = rows_per_block > 0 ? rows_per_block : auto_rows_per_block(s);

@@ -237,10 +237,16 @@ class Session:
         L.check(L.lib().dlp_session_info(h, C.byref(rows), C.byref(first), C.byref(ld),
                                          C.byref(ncols)), "dlp_session_info")
         self.rows, self.row_first, self.ld, self.ncols = rows.value, first.value, ld.value, ncols.value
-        # the tableau as stored: row stride, RHS column, condensed or full
+        self.storage()
+
+    def storage(self) -> tuple[int, int, bool]:
+        """The tableau as stored: (row stride, RHS column, condensed or full); also
+        kept in storage_ld / storage_ncols / condensed."""
         sld, snc, cond = C.c_int64(), C.c_int64(), C.c_int()
-        L.check(L.lib().dlp_session_storage(h, C.byref(sld), C.byref(snc), C.byref(cond)), "dlp_session_storage")
+        L.check(L.lib().dlp_session_storage(self._h, C.byref(sld), C.byref(snc), C.byref(cond)),
+                "dlp_session_storage")
         self.storage_ld, self.storage_ncols, self.condensed = sld.value, snc.value, bool(cond.value)
+        return self.storage_ld, self.storage_ncols, self.condensed
 
     def run(self, max_pivots: int) -> tuple[int, int]:
         done = C.c_int64()
@@ -304,6 +310,24 @@ class Session:
         ms = C.c_double()
         L.check(L.lib().dlp_session_set_rhs(self._h, _dptr(b), b.shape[0], C.byref(ms)),
                 "dlp_session_set_rhs")
+        return ms.value
+
+    def set_defer(self, defer: int, condensed: int = 0, lookahead: int = -1) -> float:
+        """Move the live session to another storage path between runs (dlp_session_set_defer):
+        defer 1 = eager, 2..64 = pivots per tableau pass, 0 = auto; condensed and lookahead
+        -1 / 0 / 1 as the creation options.  Status, pivots, basis, log and the tableau as read out
+        stay as they are.  Returns the device time (ms) of the relayout kernel (0.0 when the layout
+        stays)."""
+        for name, v, lo, hi in (("defer", defer, 0, 64), ("condensed", condensed, -1, 1),
+                                ("lookahead", lookahead, -1, 1)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{name} must be an integer, not {type(v).__name__}")
+            if not lo <= v <= hi:
+                raise ValueError(f"{name} must be in {lo}..{hi}, not {v}")
+        ms = C.c_double()
+        L.check(L.lib().dlp_session_set_defer(self._h, int(defer), int(condensed), int(lookahead),
+                                              C.byref(ms)), "dlp_session_set_defer")
+        self.storage()
         return ms.value
 
     def status(self) -> tuple[int, int]:

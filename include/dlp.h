@@ -347,7 +347,8 @@ int dlp_session_step_update(dlp_session* s);
  * created with nranks > 1 or an RCCL id; DLP_ERR_STATE: a failed session, a caller-driven step
  * in progress (step_candidate done, step_update not yet), or a dual phase that is pending or
  * ended DLP_INFEASIBLE (dlp_session_set_rhs: the RHS has negative entries).
- * Not covered: changes of A (changes of b: dlp_session_set_rhs below, eager sessions only), a
+ * Not covered: changes of A (changes of b: dlp_session_set_rhs below, eager sessions only;
+ * dlp_session_set_defer moves a live deferred session there and back), a
  * device-pointer c, multi-rank sessions, general LPs.  (Batches: dlp_batch_resolve applies this
  * rule to every resident LP.) */
 int dlp_session_set_objective(dlp_session* s, const double* c, int64_t n, double* kernel_ms);
@@ -402,8 +403,52 @@ int dlp_session_set_objective(dlp_session* s, const double* c, int64_t n, double
  *   every status.  A negative pivot leaves -0 where a +0 stood in the basic columns of the pivot row;
  *   no comparison of the rule sees the sign of a zero.
  * Not covered: deferred sessions (their replay state and RHS cache would have to be re-established
- * after the eager dual pivots), changes of A, a device-pointer b, multi-rank sessions, general LPs. */
+ * after the eager dual pivots; dlp_session_set_defer(s, 1, ...) below moves a live deferred session
+ * to the eager path first and back afterwards), changes of A, a device-pointer b, multi-rank
+ * sessions, general LPs. */
 int dlp_session_set_rhs(dlp_session* s, const double* b, int64_t m, double* kernel_ms);
+/* Move a live single-GPU session to another storage path, between runs: the eager
+ * full layout (defer = 1), or a deferred one with `defer` pivots per tableau pass, full or
+ * condensed, with or without lookahead.  A session can so solve cold on the deferred path, switch
+ * to eager for dlp_session_set_rhs and its dual phase, and switch back; or change K between phases.
+ *   defer      1 = eager, 2..64 = pivots per pass, 0 = auto: creation's size rule for this tableau;
+ *   condensed  -1 / 0 / 1 as dlp_options.condensed (DLP_CONDENSED overrides the auto choice);
+ *              ignored when the target is eager;
+ *   lookahead  -1 / 0 / 1 as dlp_options.lookahead: auto is on at K = 64 on a tableau > 1 GiB, 1 is
+ *              on where it applies (it silently stays off elsewhere, as at creation); ignored when
+ *              the target is eager;
+ *   *kernel_ms (may be NULL): device time of the relayout kernel alone, 0 when no layout changed.
+ * Unchanged by the call, bit for bit: the status (an optimal session stays optimal: the next
+ * dlp_session_run returns DLP_OK with 0 pivots; a running one continues), the pivot count, the
+ * pivot log, the basis, the Bland state, options.max_pivots' life-time count, tolerances and
+ * pricing, the requested update variant, rows_per_block and non-temporal setting.  The tableau as
+ * read out (dlp_session_tableau / _read_rows / _result) is byte-identical before and after, but for
+ * the condensed layout's known caveat: its read-out gives +0 in a basic column where the full
+ * layout may hold a -0 (after a dual phase's negative pivots).
+ * After the call dlp_session_storage, _get_defer_tuning, _get_lookahead and _chain_cus report the
+ * new path; the pass form is creation's choice for the new K (dlp_session_set_defer_tuning
+ * overrides it afterwards) and the fused pivot is off, as at creation; graph windows captured on
+ * the old geometry are dropped.  Every later pivot is bit-identical to the pivot a session created
+ * on either path would do.  After a switch to defer = 1, dlp_session_set_rhs is accepted; after a
+ * dual phase that ended DLP_OK, a switch back to a deferred path is accepted.
+ * A layout that stays (full <-> full, e.g. eager <-> condensed = -1) keeps its buffer and stride and
+ * nothing is copied; a new layout takes creation's stride rule for the session's ld_align.  The
+ * nonbasic variables enter a new condensed layout ascending by index in slots 0..n-1 (the slot
+ * order is not observable).  The old and the new tableau coexist during the call.
+ * A call that asks for the path the session already runs returns DLP_OK and touches nothing.
+ * Errors, each validated before anything is enqueued or allocated and leaving the session bit for
+ * bit as it was, checked in this order:
+ *   1. DLP_ERR_ARG: s NULL; defer outside 0..64; condensed or lookahead outside -1..1; defer > 1
+ *      with an update variant that is not a 512-column one;
+ *   2. DLP_ERR_UNSUPPORTED (text in dlp_last_error): a general or MPS problem; a session created
+ *      with nranks > 1 or an RCCL id; a session on the one-launch small-LP path
+ *      (dlp_session_small_lp = 1);
+ *   3. DLP_ERR_STATE: a failed session; a caller-driven step in progress; a dual phase that is
+ *      pending or ended DLP_INFEASIBLE (the RHS has negative entries, which no deferred primal path
+ *      may see);
+ *   4. DLP_ERR_OOM: the new buffers do not fit; they are allocated before anything is changed.
+ * Not covered: a deferred dual pivot, multi-rank and general-LP sessions. */
+int dlp_session_set_defer(dlp_session* s, int defer, int condensed, int lookahead, double* kernel_ms);
 int dlp_session_buffer(dlp_session* s, int which, void** dev_ptr, size_t* bytes);
 /* Synchronous host copies of an exchange buffer (for host-side communicators). */
 int dlp_session_read_buffer(dlp_session* s, int which, void* host, size_t bytes);
