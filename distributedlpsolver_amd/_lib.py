@@ -226,6 +226,7 @@ SIGNATURES = [
     ("dlp_batch_read", C.c_int, [_P, _I64, _DP, C.POINTER(_I32)]),
     ("dlp_batch_info", C.c_int,
      [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_I64)]),
+    ("dlp_batch_rhs_kernel", C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
     ("dlp_batch_free", None, [_P]),
 ]
 

@@ -848,6 +848,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
     __shared__ uint64_t s_zm;   // rows 0..63 of the entering column that are +-0 (the elimination's skip rule)
     __shared__ int32_t s_bad;   // dense input: some b_i is not >= 0 (resident: 1 rejected at creation, 2 a bad c_k, 3 a dual phase left it infeasible or pending)
     __shared__ double s_cb[M];  // resident, new objective: cB_i = c[basis[i]] (+0.0 for a slack)
+    // dual (RhsIn) only, absent from every other instantiation: b_k, where each slack lives (>= 0 its
+    // slot, else -(row + 1) of the row it is basic in), the continuation flag, and the staging tile
+    // of the RHS rebuild: kPanel slack columns of R entries (stride R = 65 doubles, odd: the 16
+    // writers of one row land in 16 different bank pairs, the 64 readers of one column are consecutive)
+    constexpr int kPanel = 16;
+    __shared__ double s_b[M];
+    __shared__ int32_t s_inv[M];
+    __shared__ int32_t s_cont;
+    __shared__ double s_zr;
+    __shared__ double s_stage[kPanel * R];
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int N = n + M;
     const int sl = tid;              // this lane's slot: < n a variable's column
@@ -890,6 +900,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
                 di[N] = s_bland;
                 di[N + 1] = stt;
             }
+            if constexpr (In::dual)   // the b_k this RHS column was built from
+                if (wid == 0) in.last[lp * M + lane] = s_b[lane];
         }
     };
     bool has_c = false;   // (resident) a new objective
@@ -923,10 +935,34 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
                 s_cb[lane] = bv < n ? c[bv] : 0.0;   // cB_i, staged once per LP
             }
             // 3: left infeasible or pending by a dual phase (negative RHS entries: DLP_ERR_STATE)
-            if (bad == 0 && (saved == DLP_INFEASIBLE || saved == kDualPending)) bad = 3;
-            if (lane == 0) {
-                s_bad = bad;
-                s_bland = has_c ? (pricing == DLP_PRICING_BLAND ? 1 : 0) : si[N];
+            if constexpr (!In::dual) {
+                if (bad == 0 && (saved == DLP_INFEASIBLE || saved == kDualPending)) bad = 3;
+                if (lane == 0) {
+                    s_bad = bad;
+                    s_bland = has_c ? (pricing == DLP_PRICING_BLAND ? 1 : 0) : si[N];
+                }
+            } else {
+                // 2: a b_k entry that is not finite; 3: some stored slot has z < -tol_dj (the LP is
+                // not dual feasible: stopped inside a primal solve, or unbounded).  Lane i takes
+                // b_k[i] once, for the checks, the rebuild (through LDS) and `last`.
+                const double bl = in.b[lp * in.sb + lane];
+                s_b[lane] = bl;
+                bool neg = false;
+                for (int s = lane; s < n; s += 64) neg |= rec[M * W + s] < -tol_dj;
+                if (__ballot(not_finite(bl)) != 0 && bad == 0) bad = 2;
+                if (__ballot(neg) != 0 && bad == 0) bad = 3;
+                // continuation: a pending dual phase handed the very b_k (bit for bit) it was
+                // stopped with goes on from its RHS column and Bland state as they stand
+                bool cont = saved == kDualPending;
+                if (cont) {
+                    const double ll = in.last[lp * M + lane];
+                    cont = __ballot(__builtin_bit_cast(uint64_t, bl) != __builtin_bit_cast(uint64_t, ll)) == 0;
+                }
+                if (lane == 0) {
+                    s_bad = bad;
+                    s_cont = cont ? 1 : 0;
+                    s_bland = (cont && si[N]) || pricing == DLP_PRICING_BLAND ? 1 : 0;
+                }
             }
         }
         if (has_c && own && var < n) acc = -in.c[lp * in.sc + var];
@@ -986,7 +1022,53 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
         }
     }
     int status = DLP_RUNNING;
-    if constexpr (In::resident) {
+    if constexpr (In::dual) {
+        if (s_cont == 0) {   // (uniform)
+            // The RHS rebuild (dlp.h, dlp_batch_resolve_rhs's rule) on the columns in registers:
+            // row r's new RHS is the fold of Tfull[r][n + l] * b_l over l ascending, and slack l's
+            // column sits in the lane that owns its slot, or is the unit vector of the row it is
+            // basic in (a term of exactly b_l there; elsewhere its +-0 product cannot change a bit
+            // and is left out, as in the LDS kernel).  The columns cross to the rows' lanes through
+            // the staging tile, kPanel slacks at a time: the owner of a slack of the panel writes
+            // its R entries, then wave 0's lane i folds row i, and every lane of wave 0 the
+            // objective row (each keeps zr), the accumulators carried from panel to panel.
+            if (own && var >= n) s_inv[var - n] = sl;
+            if (wid == 0) {
+                const int bv = s_basis[lane];
+                if (bv >= n) s_inv[bv - n] = -(lane + 1);
+            }
+            double ra = 0.0, za = 0.0;
+            for (int l0 = 0; l0 < M; l0 += kPanel) {
+                const int c = var - n - l0;   // (kNoIndex in a lane past the slots: never in a panel)
+                if (own && c >= 0 && c < kPanel) each<R>([&](auto I) { s_stage[c * R + I] = t[I]; });
+                __syncthreads();
+                if (wid == 0) {
+                    // (rolled: unrolled, the panel's 32 LDS reads are requested ahead of the
+                    // dependent adds and the register rows spill)
+#pragma unroll 1
+                    for (int j = 0; j < kPanel; ++j) {
+                        const int iv = s_inv[l0 + j];
+                        const double bl = s_b[l0 + j];
+                        if (iv >= 0) {
+                            ra = fold_step(ra, s_stage[j * R + lane], bl);
+                            za = fold_step(za, s_stage[j * R + M], bl);
+                        } else if (iv == -(lane + 1)) {
+                            ra = fold_step(ra, 1.0, bl);
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+            if (wid == 0) {
+                rr = ra;
+                zr = za;
+            }
+        }
+        // (the objective value lives in LDS through the dual pivot loop, thread 0's alone to read
+        // and write: the loop holds more than the primal's, and the two VGPRs are what keeps
+        // the instantiation inside 168 without scratch)
+        if (tid == 0) s_zr = zr;
+    } else if constexpr (In::resident) {
         if (has_c) {
             // The objective rebuild, on the rows just loaded (dlp.h, dlp_session_set_objective's
             // rule): the lane owns its slot's column and folds rows 0..M-1 ascending, cB_i from
@@ -1015,8 +1097,104 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
     auto stamp = [&](int ph) {
         if (out.stamps && lp == 0 && tid == 0 && k < 64) out.stamps[k * 8 + ph] = wall_clock64();
     };
-    for (; k < max_pivots; ++k) {
+    for (; In::dual || k < max_pivots; ++k) {
         stamp(0);
+        int q = kNoIndex, sq = -1, p = -1;
+        uint64_t zm = 0;
+      if constexpr (In::dual) {
+        // ---- d1 leaving row (wave 0, row = lane): the most negative RHS below -tol_feas, exact
+        // ties -> the smallest basic VARIABLE; Bland -> the eligible row with the smallest basic
+        // variable (the ratio test's ballot / wave_min_i32 pattern)
+        if (wid == 0) {
+            const bool elig = rr < -in.tol_feas;
+            const int bv = s_basis[lane];
+            int pl = -1;
+            if (__ballot(elig) != 0) {
+                if (s_bland) {
+                    const int bmin = wave_min_i32(elig ? bv : kNoIndex);
+                    pl = __ffsll((unsigned long long)__ballot(elig && bv == bmin)) - 1;
+                } else {
+                    const double rmin = wave_min_f64(elig ? rr : __builtin_inf());
+                    const bool tie = elig && rr == rmin;
+                    const uint64_t ties = __ballot(tie);
+                    pl = __ffsll((unsigned long long)ties) - 1;
+                    if (__popcll(ties) > 1) {
+                        const int bmin = wave_min_i32(tie ? bv : kNoIndex);
+                        pl = __ffsll((unsigned long long)__ballot(tie && bv == bmin)) - 1;
+                    }
+                }
+            }
+            if (lane == 0) s_p = pl;
+        }
+        __syncthreads();
+        stamp(1);
+        p = __builtin_amdgcn_readfirstlane(s_p);   // (uniform: an SGPR operand below)
+        if (p < 0) {   // primal feasible too: optimal (tested before the budget)
+            status = DLP_OK;
+            break;
+        }
+        if (k >= max_pivots) break;
+        // ---- d2 entering slot: min over a = T[p][s] < -tol_piv of max(z_s, 0) / -a, exact ties ->
+        // the smallest variable; per wave field by field, then across the waves (the pricing
+        // reduction's structure).  A NaN ratio is no candidate, a +inf one is (it loses to any
+        // finite ratio and ties by variable), as the LDS kernel's comparison has it.
+        {
+            double a = 0.0;
+            each<M / 8>([&](auto G) { if ((p >> 3) == (int)G) pick8<8 * G>(a, &t[8 * G], p); });
+            bool cand = own && a < -tol_piv;
+            double r = __builtin_inf();
+            if (cand) {
+                double zz = t[M];
+                if (!(zz > 0.0)) zz = 0.0;
+                r = zz / (-a);
+                if (r != r) {
+                    cand = false;
+                    r = __builtin_inf();
+                }
+            }
+            const double rmin = wave_min_f64(r);
+            const int vr = cand && r == rmin ? var : kNoIndex;
+            const int vmin = wave_min_i32(vr);
+            const uint64_t wz = __ballot(vr == vmin && vmin != kNoIndex);
+            if (lane == 0) {
+                s_zv[wid] = rmin;
+                s_zvar[wid] = vmin;
+                s_zslot[wid] = wz ? wid * 64 + __ffsll((unsigned long long)wz) - 1 : -1;
+            }
+        }
+        __syncthreads();
+        stamp(2);
+        double rbest = s_zv[0];
+        q = s_zvar[0], sq = s_zslot[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) {
+            if (s_zv[w] < rbest || (s_zv[w] == rbest && s_zvar[w] < q)) {
+                rbest = s_zv[w]; q = s_zvar[w]; sq = s_zslot[w];
+            }
+        }
+        if (sq < 0) {   // no entry of row p can take its RHS up: no x satisfies the row
+            status = DLP_INFEASIBLE;
+            break;
+        }
+        // ---- the entering column to LDS (its owner lane) + select and log as the primal's a4
+        if (sl == sq) each<R>([&](auto I) { s_colq[I] = t[I]; });
+        if (tid == 0) {
+            const int leaving = s_basis[p];
+            s_basis[p] = q;
+            s_leave = leaving;
+            s_bland = (pricing == DLP_PRICING_BLAND) ? 1 : (rbest == 0.0 ? 1 : 0);
+            if (out.logs && k < out.log_cap) {
+                dlp_pivot e;
+                e.q = q; e.p = p; e.leaving = leaving; e.pad = 0;
+                e.ratio = rbest; e.objective = 0.0;
+                out.logs[lp * out.log_cap + k] = e;
+            }
+        }
+        __syncthreads();
+        stamp(3);
+        // the elimination's skip masks, balloted by every wave for itself (-0 == 0: both skipped)
+        zm = __ballot(s_colq[lane] == 0.0);
+      } else {
         // ---- a1 pricing: lexicographic (z, variable) min; Bland: first variable with z < -tol.
         // Reduced field by field (min z, then the smallest variable among the lanes holding it;
         // the Bland variable apart): fewer cross-lane moves than shuffling the whole tuple.
@@ -1040,7 +1218,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
         }
         __syncthreads();
         stamp(1);
-        int q = kNoIndex, sq = -1;
         {
             double zmin = s_zv[0];
             int vmin = s_zvar[0], smin = s_zslot[0], vb = s_bvar[0], sb = s_bslot[0];
@@ -1120,18 +1297,20 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
         }
         __syncthreads();
         stamp(3);
-        const int p = __builtin_amdgcn_readfirstlane(s_p);   // (uniform: an SGPR operand below)
+        p = __builtin_amdgcn_readfirstlane(s_p);   // (uniform: an SGPR operand below)
         // the elimination's inputs, requested with p's (their LDS latency overlaps the pivot-row
         // division): the skip rule's row masks from the entering column's zero mask (SALU, no VALU
         // compare per row) and the entries for the DPP broadcast, 4 LDS reads per lane (elim8dpp)
         // (readfirstlane returns int: both halves through uint32_t, or a set bit 31 — row 31's
         // entry +-0 — sign-extends over rows 32..63 and their eliminations are skipped)
-        const uint64_t zm = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(s_zm >> 32)) << 32) |
-                            (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)s_zm);
+        zm = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(s_zm >> 32)) << 32) |
+             (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)s_zm);
+      }
         double cq[M / 16];
         each<M / 16>([&](auto G) { cq[G] = s_colq[16 * G + (lane & 15)]; });
         // (with them: the pivot, the objective row's entry and wave 0's row entry for its RHS update)
-        const double piv = s_piv, fM = s_colq[M];
+        // (the dual's pivot is the entering column's entry of row p, negative)
+        const double piv = In::dual ? s_colq[p] : s_piv, fM = s_colq[M];
         const double fr = wid == 0 ? s_colq[lane] : 0.0;
         if (p < 0) {
             status = DLP_UNBOUNDED;
@@ -1157,11 +1336,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
             const double v = __builtin_fma(-fr, pjr, rr);
             rr = lane == p ? pjr : (fr != 0.0 ? v : rr);
             const double fz = fM;
-            if (fz != 0.0) zr = __builtin_fma(-fz, pjr, zr);
+            if constexpr (In::dual) {
+                if (lane == 0 && fz != 0.0) s_zr = __builtin_fma(-fz, pjr, s_zr);
+            } else {
+                if (fz != 0.0) zr = __builtin_fma(-fz, pjr, zr);
+            }
         }
         stamp(5);
-        if (tid == 0 && out.logs && k < out.log_cap) out.logs[lp * out.log_cap + k].objective = zr;
+        if (tid == 0 && out.logs && k < out.log_cap) out.logs[lp * out.log_cap + k].objective = In::dual ? s_zr : zr;
     }
+    if constexpr (In::dual)
+        if (tid == 0) zr = s_zr;   // (store_state's and the output's copy are thread 0's)
     if (tid == 0) {
         int stt = status;
         if (stt == DLP_RUNNING) stt = DLP_PIVOT_LIMIT;
@@ -1169,7 +1354,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
         if (out.npivots) out.npivots[lp] = k;
         if (out.objective) out.objective[lp] = zr;
     }
-    store_state(status == DLP_RUNNING ? (int)DLP_PIVOT_LIMIT : status);
+    // (a dual phase the budget stopped is stored as pending: the primal rule must not continue it)
+    store_state(status == DLP_RUNNING ? (In::dual ? kDualPending : (int)DLP_PIVOT_LIMIT) : status);
     if (out.basis)
         for (int i = tid; i < M; i += blockDim.x) out.basis[lp * M + i] = s_basis[i];
     // x and y from the tableau as it stands, every index written exactly once (no zero fill):
@@ -1240,6 +1426,13 @@ hipError_t ensure_buf(void** p, size_t* cap, size_t bytes, bool pinned = false) 
     const hipError_t e = pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
     if (e == hipSuccess) *cap = bytes;
     return e;
+}
+
+// DLP_BATCH_RHS_LDS=1: dlp_batch_resolve_rhs runs the LDS kernel at every shape (A/B against the
+// register instantiation); read once per process, as DLP_BATCH_LDS
+bool rhs_force_lds() {
+    static const bool f = dlp::env_int("DLP_BATCH_RHS_LDS", 0) == 1;
+    return f;
 }
 
 // restores the caller's current device on every return path
@@ -1523,9 +1716,9 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
         // kernel, for A/B); otherwise the LDS-resident one
         static const bool force_lds = dlp::env_int("DLP_BATCH_LDS", 0) == 1;
         const int nw = (int)((n + 63) / 64);
-        // (the dual re-solve has an LDS instantiation only: m = 64 goes through it for that call,
-        // on the same records)
-        const bool reg = !force_lds && m == 64 && nw >= 1 && nw <= 3 && !job.rhs;
+        // (the dual re-solve runs the register kernel's RhsIn instantiation on the same records;
+        // DLP_BATCH_RHS_LDS=1 sends that call alone through the LDS kernel)
+        const bool reg = !force_lds && m == 64 && nw >= 1 && nw <= 3 && !(job.rhs && rhs_force_lds());
         // the kernel of this input kind (its own instantiation, so its own dynamic-LDS attribute),
         // timed alone between e0 and e1
         auto launch = [&](auto in) -> hipError_t {
@@ -1537,17 +1730,15 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
             if (e == hipSuccess) e = hipEventRecord(c->e0, s);
             if (e != hipSuccess) return e;
             if (reg) {
-                if constexpr (!In::dual) {   // (reg is false for the dual source)
-                    if (nw == 1)
-                        dlp::batched_reg_kernel<64, 1, In><<<(unsigned)nlp, 64, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
-                                                                                      o.tol_dj, o.tol_piv, bo);
-                    else if (nw == 2)
-                        dlp::batched_reg_kernel<64, 2, In><<<(unsigned)nlp, 128, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
-                                                                                       o.tol_dj, o.tol_piv, bo);
-                    else
-                        dlp::batched_reg_kernel<64, 3, In><<<(unsigned)nlp, 192, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
-                                                                                       o.tol_dj, o.tol_piv, bo);
-                }
+                if (nw == 1)
+                    dlp::batched_reg_kernel<64, 1, In><<<(unsigned)nlp, 64, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
+                                                                                  o.tol_dj, o.tol_piv, bo);
+                else if (nw == 2)
+                    dlp::batched_reg_kernel<64, 2, In><<<(unsigned)nlp, 128, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
+                                                                                   o.tol_dj, o.tol_piv, bo);
+                else
+                    dlp::batched_reg_kernel<64, 3, In><<<(unsigned)nlp, 192, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
+                                                                                   o.tol_dj, o.tol_piv, bo);
             } else {
                 // 512 lanes per LP when few LPs share a CU (LDS > 40 KB each), else 256
                 const unsigned threads = lds > 40 * 1024 ? 512 : 256;
@@ -1775,6 +1966,47 @@ extern "C" int dlp_batch_info(const dlp_batch* batch, int64_t* nlp, int64_t* m, 
     if (n) *n = batch->n;
     if (register_kernel) *register_kernel = batch->reg ? 1 : 0;
     if (device_bytes) *device_bytes = batch->bytes;
+    return DLP_OK;
+}
+
+// The kernel dlp_batch_resolve_rhs runs for this batch (batched_run's choice) and how many LPs one
+// CU of the batch's device holds of it: the occupancy query on that very instantiation.
+extern "C" int dlp_batch_rhs_kernel(const dlp_batch* batch, int32_t* register_kernel, int32_t* lps_per_cu,
+                                    int32_t* threads_per_lp) {
+    if (!batch) {
+        dlp::set_error("dlp_batch_rhs_kernel: bad arguments");
+        return DLP_ERR_ARG;
+    }
+    using dlp::RhsIn;
+    const int64_t m = batch->m, n = batch->n;
+    const size_t lds = sizeof(double) * ((m + 1) * (n + 1) + (m + 1) + (n + 1)) + sizeof(int32_t) * (n + m + 8) +
+                       sizeof(double) * 2 + 16;
+    static const bool force_lds = dlp::env_int("DLP_BATCH_LDS", 0) == 1;
+    const int nw = (int)((n + 63) / 64);
+    const bool reg = !force_lds && m == 64 && nw >= 1 && nw <= 3 && !rhs_force_lds();
+    DeviceGuard guard;
+    if (hipSetDevice(batch->opt.device) != hipSuccess) return DLP_ERR_HIP;
+    int nb = 0, threads = 0;
+    hipError_t e;
+    if (reg) {
+        threads = 64 * nw;
+        e = nw == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dlp::batched_reg_kernel<64, 1, RhsIn>, threads, 0)
+          : nw == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dlp::batched_reg_kernel<64, 2, RhsIn>, threads, 0)
+                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dlp::batched_reg_kernel<64, 3, RhsIn>, threads, 0);
+    } else {
+        threads = lds > 40 * 1024 ? 512 : 256;
+        e = hipFuncSetAttribute((const void*)dlp::batched_solve_kernel<RhsIn>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess)
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dlp::batched_solve_kernel<RhsIn>, threads, lds);
+    }
+    if (e != hipSuccess) {
+        dlp::set_error(std::string("dlp_batch_rhs_kernel: ") + hipGetErrorString(e));
+        return DLP_ERR_HIP;
+    }
+    if (register_kernel) *register_kernel = reg ? 1 : 0;
+    if (lps_per_cu) *lps_per_cu = nb;
+    if (threads_per_lp) *threads_per_lp = threads;
     return DLP_OK;
 }
 

@@ -755,6 +755,15 @@ class Batch:
         return {"nlp": nlp.value, "m": m.value, "n": n.value, "register_kernel": bool(reg.value),
                 "device_bytes": db.value}
 
+    def rhs_kernel(self) -> dict:
+        """dlp_batch_rhs_kernel: the kernel resolve_rhs runs for this batch (the register kernel
+        at m = 64, n <= 192 unless DLP_BATCH_LDS=1 or DLP_BATCH_RHS_LDS=1) and its residency on
+        the batch's device.  info()["register_kernel"] keeps reporting the kernel of creation."""
+        reg, lps, thr = C.c_int32(), C.c_int32(), C.c_int32()
+        L.check(L.lib().dlp_batch_rhs_kernel(self._handle(), C.byref(reg), C.byref(lps), C.byref(thr)),
+                "dlp_batch_rhs_kernel")
+        return {"register_kernel": bool(reg.value), "lps_per_cu": lps.value, "threads_per_lp": thr.value}
+
     def close(self):
         if self._h:
             L.lib().dlp_batch_free(self._h)

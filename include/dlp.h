@@ -749,11 +749,21 @@ int dlp_batch_resolve(dlp_batch* batch, const double* c, int64_t stridec, int c_
  * Call-level errors (validated before anything is enqueued, the batch unchanged): DLP_ERR_ARG
  *   for a NULL batch or b, a stride that is neither 0 nor >= m, b_is_device not 0 / 1, negative
  *   max_pivots or log_cap.
+ * Kernel: at m = 64, n <= 192 the call runs the register-resident kernel, as creation and
+ *   dlp_batch_resolve do; at every other shape, or with DLP_BATCH_LDS=1 or
+ *   DLP_BATCH_RHS_LDS=1 in the environment, the LDS kernel.  Both give the same bits;
+ *   dlp_batch_rhs_kernel says which one runs.
  * Not covered: changes of A, c and b in one call, general LPs.  (Single sessions:
  * dlp_session_set_rhs applies this rule to an eager session's tableau; deferred sessions remain
  * the gap.) */
 int dlp_batch_resolve_rhs(dlp_batch* batch, const double* b, int64_t strideb, int b_is_device,
                           int64_t max_pivots, const dlp_batch_out* out);
+/* The kernel dlp_batch_resolve_rhs runs for this batch: *register_kernel 1 the register-resident
+ * kernel, 0 the LDS kernel; how many LPs one CU of the batch's device holds of it at once (the
+ * occupancy query on that very instantiation) and its threads per LP.  NULL outputs are skipped;
+ * a NULL batch is DLP_ERR_ARG.  (dlp_batch_info's register_kernel stays the kernel of creation.) */
+int dlp_batch_rhs_kernel(const dlp_batch* batch, int32_t* register_kernel, int32_t* lps_per_cu,
+                         int32_t* threads_per_lp);
 /* LP k's resident tableau in the full layout of dlp_session_tableau ((m+1) x dlp_tableau_ld(m,n),
  * basic columns as exact unit vectors, their objective entries +0.0, padding +0.0) and its
  * basis (m entries).  Either pointer may be NULL. */

@@ -9,6 +9,9 @@ kernel, 3 warm-ups, min / median / max over --reps repeats, no profiler attached
    dlp_batch_resolve_rhs(b2) from the optimum of b, cold is dlp_batched_solve_dense(A, b2, c).
 2. The floor: dlp_batch_resolve_rhs with the unchanged b (load, rebuild, one eligibility test,
    store) beside dlp_batch_resolve(NULL) (load, store).
+   With --other-lib the same child also runs the parent commit's library, alternating with this
+   commit's (other, this, other, this; the same b2 sequence in each), and the report says
+   whether this commit's median warm time lies below the parent's minimum.
 3. Nothing existing got slower: dlp_batched_solve_dense and dlp_batch_resolve(c2) of the
    parent commit's library (--other-lib) against this commit's, in child processes of their
    own that alternate between the two libraries (plain ctypes, so a child also runs a library
@@ -89,15 +92,24 @@ def child_existing(lib_path, m, n, reps):
     return res
 
 
-def child_rhs(m, n, reps):
-    """This commit's dlp_batch_resolve_rhs: warm against cold for both scales, then the floor."""
+def child_rhs(m, n, reps, lib_path=None):
+    """dlp_batch_resolve_rhs of the library at lib_path (default: this commit's) through the
+    package: warm against cold for both scales, then the floor.  A library of an older commit
+    is bound with the entry points it has."""
     np, torch, (A, b, c), (tA, tb, tc) = _inputs(m, n)
+    from distributedlpsolver_amd import _lib as L
+    if lib_path:
+        probe = C.CDLL(lib_path)
+        L.LIB_PATH = lib_path
+        L.SIGNATURES = [sig for sig in L.SIGNATURES if hasattr(probe, sig[0])]
     import distributedlpsolver_amd as dlp
-    out = {"occupancy": dlp.batched_occupancy(m, n)}
+    out = {"library": lib_path or THIS_LIB, "occupancy": dlp.batched_occupancy(m, n)}
     rng = np.random.default_rng(SEED)
     with dlp.Batch(tA, tb, tc) as bt:
         assert (bt.result.status == 0).all()
         out["register_kernel_of_creation"] = bt.info()["register_kernel"]
+        # (the kernel of the dual call: libraries before dlp_batch_rhs_kernel ran the LDS kernel)
+        out["rhs_kernel"] = bt.rhs_kernel() if hasattr(L.lib(), "dlp_batch_rhs_kernel") else None
         for scale in SCALES:
             res = {k: [] for k in ("warm_kernel_ms", "warm_wall_ms", "warm_pivots", "warm_max_pivots", "cold_kernel_ms",
                                    "cold_wall_ms", "cold_pivots", "max_rel_objective_diff", "back_kernel_ms",
@@ -154,16 +166,34 @@ def main():
     a = ap.parse_args()
     if a.child:
         kind, m, n = a.child[0], int(a.child[1]), int(a.child[2])
-        print(json.dumps(child_existing(a.child[3], m, n, a.reps) if kind == "existing" else child_rhs(m, n, a.reps)))
+        print(json.dumps(child_existing(a.child[3], m, n, a.reps) if kind == "existing"
+                         else child_rhs(m, n, a.reps, a.child[3] if len(a.child) > 3 else None)))
         return
     reps = ["--reps", str(a.reps)]
     report = {"nlp": NLP, "seed": SEED, "warmup": WARM, "reps_per_child": a.reps, "shapes": {}}
     for m, n in SHAPES:
-        sh = {"rhs": spawn(reps + ["--child", "rhs", str(m), str(n)])}
-        for scale in SCALES:
-            r = sh["rhs"][f"scale_{scale}"]
-            sh[f"scale_{scale}"] = {k: spread(v) for k, v in r.items()}
-        sh["floor"] = {k: spread(v) for k, v in sh["rhs"]["floor"].items()}
+        # the dual call itself, the same b2 sequence in every child: other, this, other, this
+        rhs = {"this": [], "other": []}
+        for _ in range(2 if a.other_lib else 1):
+            if a.other_lib:
+                rhs["other"].append(spawn(reps + ["--child", "rhs", str(m), str(n), a.other_lib]))
+            rhs["this"].append(spawn(reps + ["--child", "rhs", str(m), str(n)]))
+        sh = {"rhs": rhs}
+        for who, tag in (("this", ""), ("other", "_other")):
+            if not rhs[who]:
+                continue
+            for scale in SCALES:
+                keys = rhs[who][0][f"scale_{scale}"].keys()
+                sh[f"scale_{scale}{tag}"] = {k: spread([x for r in rhs[who] for x in r[f"scale_{scale}"][k]])
+                                             for k in keys}
+            sh[f"floor{tag}"] = {k: spread([x for r in rhs[who] for x in r["floor"][k]])
+                                 for k in rhs[who][0]["floor"]}
+        if a.other_lib:   # the yardstick of DESIGN.md §23: this median below the parent's minimum
+            for scale in SCALES:
+                sh[f"scale_{scale}_warm_median_below_parent_min"] = (
+                    sh[f"scale_{scale}"]["warm_kernel_ms"]["median"] < sh[f"scale_{scale}_other"]["warm_kernel_ms"]["min"])
+                sh[f"scale_{scale}_warm_pivots_identical"] = (
+                    rhs["this"][0][f"scale_{scale}"]["warm_pivots"] == rhs["other"][0][f"scale_{scale}"]["warm_pivots"])
         runs = {"this": [], "other": []}
         for _ in range(2):   # other, this, other, this: the libraries alternate
             if a.other_lib:
