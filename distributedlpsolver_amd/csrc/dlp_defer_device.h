@@ -71,3 +71,48 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
 }
 
 constexpr int kAuxSc1 = 16;   // buffer-op cache policy: sc1 (write-through store / L2 load)
+
+// The commit of a block step (the primal chain of dlp_chain.hip, which documents it, and the dual
+// chain of dlp_dual.hip): P[s] := pr for columns j, j+1; objective row z -= z_q * P[s] (z_q != 0);
+// pricing partial of this 512-column tile (pp[tile]); objective value into log[klog].
+template <int ZQ = 0>
+__device__ inline void commit_row(double* __restrict__ T, int64_t ld, int64_t rows, int64_t ncols,
+                                  int64_t nprice, int64_t klog, const double* __restrict__ C,
+                                  int64_t ldc, double* __restrict__ P, int s, int64_t j, d2 pr,
+                                  PricePart* pp, int tile, double tol_dj, dlp_pivot* log, int64_t log_cap,
+                                  PricePart* lds_pp, d2 zpre = d2{0.0, 0.0}, double zqv = 0.0,
+                                  Cond cd = Cond{}, int32_t sq = -1, int32_t bser = 0) {
+    const int64_t width = (ncols + 16) & ~(int64_t)15;
+    const bool rx = cd.on && j == sq, ry = cd.on && j + 1 == sq;
+    if (j < ld) {
+        *(d2*)(P + (int64_t)s * ld + j) = pr;
+        if (s == 0)   // block start: pivot rows 1..K-1 := +0 (see the ratio kernel's C tails)
+            for (int64_t l = 1; l < ldc; ++l) *(d2*)(P + l * ld + j) = d2{0.0, 0.0};
+        if (rx || ry) {
+            for (int l = 0; l < s; ++l) P[(int64_t)l * ld + sq] = 0.0;
+            cd.rst[sq] = (bser << 7) | s;
+        }
+    }
+    const double zq = ZQ == 0 ? C[rows * ldc + s] : zqv;
+    PricePart acc = pp_empty();
+    if (j < width) {
+        double* zp = T + rows * ld + j;
+        d2 z = ZQ == 1 ? zpre : *(const d2*)zp;
+        if (rx) z.x = 0.0;
+        if (ry) z.y = 0.0;
+        if (zq != 0.0) {
+            z.x = __builtin_fma(-zq, pr.x, z.x);
+            z.y = __builtin_fma(-zq, pr.y, z.y);
+        }
+        if (zq != 0.0 || rx || ry) *(d2*)zp = z;
+        if (cd.on)
+            price_pair_var(acc, z.x, z.y, cd.var_of[j], cd.var_of[j + 1], tol_dj);
+        else
+            price_pair(acc, z.x, z.y, j, nprice, tol_dj);
+        if (log && j <= ncols && ncols < j + 2) {
+            if (klog >= 0 && klog < log_cap) log[klog].objective = (ncols == j) ? z.x : z.y;
+        }
+    }
+    acc = block_price(acc, lds_pp);
+    if (threadIdx.x == 0) pp[tile] = acc;
+}

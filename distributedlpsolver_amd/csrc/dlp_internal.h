@@ -371,6 +371,25 @@ hipError_t launch_dual_row(const Geometry& g, const int32_t* basis, DevState* st
                            double tol_feas, hipStream_t s);
 hipError_t launch_dual_col(const Geometry& g, int32_t* basis, DevState* st, Cand* partials, double tol_piv,
                            int pricing, dlp_pivot* log, int64_t log_cap, hipStream_t s);
+// The dual phase of a deferred single-rank session, full or condensed (dlp_session_set_rhs_in_place,
+// DESIGN.md §24).  rhs_rebuild_cond: the fold on the condensed layout (a full-layout deferred session
+// uses launch_rhs_rebuild).  One dual step of a block is four launches, in this order: dual_row_defer
+// (the RHS cache d.rhs advanced by the block's last step, the leaving row, or DLP_OK), dual_rowp_defer
+// (row p replayed into raw[ld], the entering slot and the selection, or DLP_INFEASIBLE),
+// dual_colq_defer (column q replayed into d.C / d.Cc / d.nzc), dual_commit_defer (raw / pivot into
+// d.P, the objective row, pricing partials, the log).  The block is applied by launch_flush_defer.
+// partials: dual_defer_parts(g) entries.
+int dual_defer_parts(const Geometry& g);
+hipError_t launch_rhs_rebuild_cond(const Geometry& g, int64_t n, int64_t m, const int32_t* basis,
+                                   const double* b, DevState* st, int pricing, hipStream_t s);
+hipError_t launch_dual_row_defer(const Geometry& g, const Defer& d, const int32_t* basis, DevState* st,
+                                 Cand* partials, double tol_feas, hipStream_t s);
+hipError_t launch_dual_rowp_defer(const Geometry& g, const Defer& d, int32_t* basis, DevState* st, double* raw,
+                                  Cand* partials, double tol_piv, int pricing, dlp_pivot* log, int64_t log_cap,
+                                  hipStream_t s);
+hipError_t launch_dual_colq_defer(const Geometry& g, const Defer& d, const DevState* st, hipStream_t s);
+hipError_t launch_dual_commit_defer(const Geometry& g, const Defer& d, const DevState* st, const double* raw,
+                                    PricePart* pp, double tol_dj, dlp_pivot* log, int64_t log_cap, hipStream_t s);
 
 // dlp_relayout.hip: the stored tableau between the condensed and the full layout
 // (dlp_session_set_defer).  rows_total: the constraint rows and the objective row.

@@ -187,12 +187,13 @@ struct dlp_session {
     double* ro_c = nullptr;
     int32_t* ro_basic = nullptr;
     hipEvent_t ro_ev[2] = {nullptr, nullptr};
-    // dlp_session_set_rhs, allocated at its first call: b on the device, the
+    // dlp_session_set_rhs and _set_rhs_in_place, allocated at the first call: b on the device, the
     // partials of the two dual selections, the rebuild kernel's events.  dual: the session is in
     // the dual phase that call started (dlp_session_run does dual pivots) until
     // dlp_session_set_objective starts a primal one; dual_pending(): the RHS may be negative.
     double* du_b = nullptr;
     dlp::Cand* du_part = nullptr;
+    double* du_row = nullptr;   // deferred dual chain: the raw replayed pivot row (ld doubles)
     hipEvent_t du_ev[2] = {nullptr, nullptr};
     bool dual = false;
     bool graph_dual = false;   // the captured window holds dual pivots
@@ -550,7 +551,7 @@ void free_session(dlp_session* s) {
     void* dev[] = {s->Tb[0] ? s->Tb[0] : s->T, s->Tb[1], s->colq, s->prow_send, s->partials,
                    s->cand_send, s->cand_recv, s->pp, s->basis, s->st, s->log, s->d.C, s->d.Cc,
                    s->d.P, s->d.rhs, s->d.nzc, s->cl_gran, s->band_cnt, s->g.cd.slot_of, s->g.cd.var_of,
-                   s->g.cd.rst, s->ro_rows, s->ro_cb, s->ro_c, s->ro_basic, s->du_b, s->du_part};
+                   s->g.cd.rst, s->ro_rows, s->ro_cb, s->ro_c, s->ro_basic, s->du_b, s->du_part, s->du_row};
     for (void* p : dev) pool_release(s, s->device, p);
     for (hipEvent_t e : s->ro_ev)
         if (e) (void)hipEventDestroy(e);
@@ -1570,7 +1571,38 @@ int dual_step_refused(const char* fn) {
     return DLP_ERR_STATE;
 }
 
+// One dual pivot of a deferred session (dlp_session_set_rhs_in_place accepted it:
+// single rank, no lookahead): step since_flush of the block through the four launches of
+// dlp_dual.hip, then the primal's pass when the block is full or `last` (pivot_defer_phase's phase
+// 2).  A plain chain: every launch is a no-op once the status is not running, the pass applies the
+// steps the device counted.  Timing events as pivot_defer_phase records them (the two selections are
+// the ratio phase; the column replay and the commit the pivot-row phase).
+int enqueue_dual_pivot_defer(dlp_session* s, int64_t slot, bool last) {
+    const dlp_options& o = s->opt;
+    hipEvent_t* ev = s->ev_per_pivot == 5 ? &s->ev[(size_t)slot * 5] : nullptr;
+    hipEvent_t* evp = s->ev_per_pivot == 2 ? &s->ev[(size_t)slot * 2] : nullptr;
+    if (ev) HIP_TRY(hipEventRecord(ev[0], s->stream));
+    HIP_TRY(dlp::launch_dual_row_defer(s->g, s->d, s->basis, s->st, s->du_part, o.tol_feas, s->stream));
+    HIP_TRY(dlp::launch_dual_rowp_defer(s->g, s->d, s->basis, s->st, s->du_row, s->du_part, o.tol_piv, o.pricing,
+                                        s->log, s->log_cap, s->stream));
+    if (ev) HIP_TRY(hipEventRecord(ev[1], s->stream));
+    if (ev) HIP_TRY(hipEventRecord(ev[2], s->stream));
+    HIP_TRY(dlp::launch_dual_colq_defer(s->g, s->d, s->st, s->stream));
+    HIP_TRY(dlp::launch_dual_commit_defer(s->g, s->d, s->st, s->du_row, s->pp, o.tol_dj, s->log, s->log_cap,
+                                          s->stream));
+    if (ev) HIP_TRY(hipEventRecord(ev[3], s->stream));
+    s->since_flush += 1;
+    const bool flush = last || s->since_flush >= s->d.K;
+    if (flush && evp) HIP_TRY(hipEventRecord(evp[0], s->stream));
+    if (flush) CALL_TRY(enqueue_flush(s));
+    if (flush && evp) HIP_TRY(hipEventRecord(evp[1], s->stream));
+    if (ev) HIP_TRY(hipEventRecord(ev[4], s->stream));
+    if (ev || evp) s->ev_flush[slot] = flush ? 1 : 0;
+    return DLP_OK;
+}
+
 int enqueue_pivot(dlp_session* s, int64_t slot, bool last = true) {
+    if (s->dual && s->d.K > 1) return enqueue_dual_pivot_defer(s, slot, last);
     if (s->dual) return enqueue_dual_pivot(s, slot);
     for (int ph = 0; ph < 3; ++ph) CALL_TRY(pivot_phase(s, ph, slot, last));
     return DLP_OK;
@@ -2925,8 +2957,13 @@ int dlp_session_run(dlp_session* s, int64_t max_pivots, int64_t* pivots_done) {
     }
     // a dual phase tests "no row is eligible" before any budget: a tableau that
     // this call's last pivot, or the rebuild alone, made feasible is reported DLP_OK at once
+    // (a deferred session's windows end on an applied block: its leaving-row kernel reads T here)
     if (s->dual && s->status == DLP_RUNNING) {
-        HIP_TRY(dlp::launch_dual_row(s->g, s->basis, s->st, s->du_part, s->opt.tol_feas, s->stream));
+        if (s->d.K > 1)
+            HIP_TRY(dlp::launch_dual_row_defer(s->g, s->d, s->basis, s->st, s->du_part, s->opt.tol_feas,
+                                               s->stream));
+        else
+            HIP_TRY(dlp::launch_dual_row(s->g, s->basis, s->st, s->du_part, s->opt.tol_feas, s->stream));
         CALL_TRY(poll(s));
     }
     if (pivots_done) *pivots_done = s->npivots - start;
@@ -3141,42 +3178,44 @@ int dlp_session_set_objective(dlp_session* s, const double* c, int64_t n, double
 // new RHS column (the fold of dlp_dual.hip) and dual pivots from the basis as it stands
 // (dlp_session_run).  Everything is validated before anything is enqueued, so an error leaves the
 // session as it was.
-int dlp_session_set_rhs(dlp_session* s, const double* b, int64_t m, double* kernel_ms) {
+static int set_rhs_impl(dlp_session* s, const double* b, int64_t m, double* kernel_ms, bool in_place) {
     if (!s || !b) return DLP_ERR_ARG;
+    const std::string fn = in_place ? "dlp_session_set_rhs_in_place" : "dlp_session_set_rhs";
     const int64_t m_user = s->general ? s->prob_dims.m : s->m;
     if (m != m_user) {
-        set_error("dlp_session_set_rhs: b has " + std::to_string(m) + " entries, the problem " +
+        set_error(fn + ": b has " + std::to_string(m) + " entries, the problem " +
                   std::to_string(m_user) + " rows");
         return DLP_ERR_ARG;
     }
     for (int64_t i = 0; i < m; ++i)
         if (!std::isfinite(b[i])) {
-            set_error("dlp_session_set_rhs: b[" + std::to_string(i) + "] is not finite");
+            set_error(fn + ": b[" + std::to_string(i) + "] is not finite");
             return DLP_ERR_ARG;
         }
     if (s->general) {
-        set_error("dlp_session_set_rhs: general / MPS problems are not supported (their right-hand sides "
+        set_error(fn + ": general / MPS problems are not supported (their right-hand sides "
                   "live in the standard form's rows and its Phase I)");
         return DLP_ERR_UNSUPPORTED;
     }
     if (s->nranks > 1 || s->exchange) {
-        set_error("dlp_session_set_rhs: single-GPU sessions only (the dual selections would cross the "
+        set_error(fn + ": single-GPU sessions only (the dual selections would cross the "
                   "ranks of a row-block session)");
         return DLP_ERR_UNSUPPORTED;
     }
-    if (s->d.K > 1 || s->la || s->g.cd.on) {
-        set_error("dlp_session_set_rhs: a deferred session (defer = " + std::to_string(s->d.K) +
+    const bool deferred = s->d.K > 1 || s->la || s->g.cd.on;
+    if (deferred && !in_place) {
+        set_error(fn + ": a deferred session (defer = " + std::to_string(s->d.K) +
                   ") is not supported: its replay state and RHS cache would have to be re-established "
                   "after the eager dual pivots; create the session with defer = 1 or call "
                   "dlp_session_set_defer(s, 1, ...) first");
         return DLP_ERR_UNSUPPORTED;
     }
     if (s->status < 0) {
-        set_error("dlp_session_set_rhs: the session has failed");
+        set_error(fn + ": the session has failed");
         return DLP_ERR_STATE;
     }
     if (s->step_open) {
-        set_error("dlp_session_set_rhs: a caller-driven step is in progress (finish it with "
+        set_error(fn + ": a caller-driven step is in progress (finish it with "
                   "dlp_session_step_update)");
         return DLP_ERR_STATE;
     }
@@ -3184,34 +3223,68 @@ int dlp_session_set_rhs(dlp_session* s, const double* b, int64_t m, double* kern
     // dual feasibility: the objective row and the basis as the device has them (reads only)
     std::vector<int32_t> basis(s->m);
     std::vector<double> z(s->N);
-    HIP_TRY(hipMemcpyAsync(basis.data(), s->basis, sizeof(int32_t) * s->m, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipMemcpyAsync(z.data(), s->T + s->rows * s->ld, sizeof(double) * s->N, hipMemcpyDeviceToHost,
-                           s->stream));
-    CALL_TRY(poll(s));   // (synchronises the stream; npivots and status as the device has them)
-    {
+    if (s->g.cd.on) {
+        // the stored layout: every slot holds a nonbasic variable (var_of names it); the objective row
+        // is kept current in place whatever the open block holds, in the lookahead's z buffer
+        const double* zrow = (s->la ? s->Tb[s->zbuf] : s->T) + s->rows * s->ld;
+        std::vector<int32_t> var_of(s->n);
+        HIP_TRY(hipMemcpyAsync(z.data(), zrow, sizeof(double) * s->n, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(var_of.data(), s->g.cd.var_of, sizeof(int32_t) * s->n, hipMemcpyDeviceToHost,
+                               s->stream));
+        CALL_TRY(poll(s));
+        for (int64_t sl = 0; sl < s->n; ++sl)
+            if (var_of[sl] >= 0 && z[sl] < -s->opt.tol_dj) {
+                set_error(fn + ": the tableau is not dual feasible (z[" + std::to_string(var_of[sl]) +
+                          "] = " + std::to_string(z[sl]) + " < -tol_dj: a session stopped inside a primal "
+                          "solve, or an unbounded one); run it to DLP_OK first");
+                return DLP_ERR_STATE;
+            }
+    } else {
+        const double* zrow = (s->la ? s->Tb[s->zbuf] : s->T) + s->rows * s->ld;
+        HIP_TRY(hipMemcpyAsync(basis.data(), s->basis, sizeof(int32_t) * s->m, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(z.data(), zrow, sizeof(double) * s->N, hipMemcpyDeviceToHost, s->stream));
+        CALL_TRY(poll(s));   // (synchronises the stream; npivots and status as the device has them)
         std::vector<uint8_t> basic(s->N, 0);
         for (int64_t i = 0; i < s->m; ++i)
             if (basis[i] >= 0 && basis[i] < s->N) basic[basis[i]] = 1;
         for (int64_t j = 0; j < s->N; ++j)
             if (!basic[j] && z[j] < -s->opt.tol_dj) {
-                set_error("dlp_session_set_rhs: the tableau is not dual feasible (z[" + std::to_string(j) +
+                set_error(fn + ": the tableau is not dual feasible (z[" + std::to_string(j) +
                           "] = " + std::to_string(z[j]) + " < -tol_dj: a session stopped inside a primal "
                           "solve, or an unbounded one); run it to DLP_OK first");
                 return DLP_ERR_STATE;
             }
     }
+    if (deferred) {
+        // the dual blocks are single-buffer ones (the step API's rule): the lookahead drained and
+        // off, a block the step API left open applied; T and the objective row both in s->T
+        if (s->la) {
+            CALL_TRY(la_disable(s));
+            drop_graph(s);
+        }
+        CALL_TRY(flush_pending(s));
+    }
     // (each on its own: a call that failed half-way through them leaves the rest for the next one)
     if (!s->du_b)
         HIP_TRY(pool_alloc(s, s->device, (void**)&s->du_b, sizeof(double) * std::max<int64_t>(s->m, 1)));
     if (!s->du_part) {
-        const int64_t parts = std::max(dlp::dual_row_blocks(s->g), dlp::dual_col_blocks(s->g));
+        const int64_t parts = std::max<int64_t>(std::max(dlp::dual_row_blocks(s->g), dlp::dual_col_blocks(s->g)),
+                                                dlp::dual_defer_parts(s->g));
         HIP_TRY(pool_alloc(s, s->device, (void**)&s->du_part, sizeof(dlp::Cand) * parts));
+    }
+    if (deferred && !s->du_row) {
+        HIP_TRY(pool_alloc(s, s->device, (void**)&s->du_row, sizeof(double) * s->ld));
+        HIP_TRY(hipMemsetAsync(s->du_row, 0, sizeof(double) * s->ld, s->stream));
     }
     for (hipEvent_t& e : s->du_ev)
         if (!e) HIP_TRY(hipEventCreate(&e));
     HIP_TRY(hipMemcpyAsync(s->du_b, b, sizeof(double) * m, hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipEventRecord(s->du_ev[0], s->stream));
-    HIP_TRY(dlp::launch_rhs_rebuild(s->g, s->n, s->du_b, s->st, s->opt.pricing, s->stream));
+    if (s->g.cd.on)
+        HIP_TRY(dlp::launch_rhs_rebuild_cond(s->g, s->n, s->m, s->basis, s->du_b, s->st, s->opt.pricing,
+                                             s->stream));
+    else
+        HIP_TRY(dlp::launch_rhs_rebuild(s->g, s->n, s->du_b, s->st, s->opt.pricing, s->stream));
     HIP_TRY(hipEventRecord(s->du_ev[1], s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     if (kernel_ms) {
@@ -3225,6 +3298,16 @@ int dlp_session_set_rhs(dlp_session* s, const double* b, int64_t m, double* kern
     s->launched = s->npivots;
     s->dual = true;
     return DLP_OK;
+}
+
+int dlp_session_set_rhs(dlp_session* s, const double* b, int64_t m, double* kernel_ms) {
+    return set_rhs_impl(s, b, m, kernel_ms, false);
+}
+
+// The same for every storage path: a deferred session keeps its path, its dual
+// phase runs in blocks of K through the deferred dual chain of dlp_dual.hip and the primal's pass.
+int dlp_session_set_rhs_in_place(dlp_session* s, const double* b, int64_t m, double* kernel_ms) {
+    return set_rhs_impl(s, b, m, kernel_ms, true);
 }
 
 // Storage switch of a live session: another K, another layout, lookahead on or off,
@@ -3427,6 +3510,7 @@ int dlp_session_set_defer(dlp_session* s, int defer, int condensed, int lookahea
                         s->dslot[1].C != old.d.C ? s->dslot[1].nzc : nullptr,
                         s->band_cnt,
                         relayout ? s->du_part : nullptr,
+                        relayout ? s->du_row : nullptr,
                         cond ? s->ro_basic : nullptr};
         for (void* p : gone) pool_release(s, s->device, p);
         s->Tb[0] = s->T;
@@ -3435,6 +3519,7 @@ int dlp_session_set_defer(dlp_session* s, int defer, int condensed, int lookahea
         s->band_cnt = nullptr;
         s->band_stride = 0;
         if (relayout) s->du_part = nullptr;
+        if (relayout) s->du_row = nullptr;
         if (cond) s->ro_basic = nullptr;
     }
     s->tread = s->tcur = s->zbuf = s->cur = 0;

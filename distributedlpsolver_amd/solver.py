@@ -296,10 +296,12 @@ class Session:
                 "dlp_session_set_objective")
         return ms.value
 
-    def set_rhs(self, b) -> float:
+    def set_rhs(self, b, in_place: bool = False) -> float:
         """Replace the right-hand side by b (m float64 values, any sign) and put the session into
         a dual phase from its current basis (dlp_session_set_rhs: a warm re-solve; run() then does
-        dual pivots and ends OK or INFEASIBLE).  Eager and small-LP sessions of an optimal tableau.
+        dual pivots and ends OK or INFEASIBLE).  Eager and small-LP sessions of an optimal tableau;
+        in_place=True (dlp_session_set_rhs_in_place) also accepts a deferred session, whose dual
+        phase then runs on its own path in blocks of K (a lookahead is drained and turned off).
         Returns the device time (ms) of the RHS rebuild."""
         b = np.asarray(b)
         if b.dtype.kind not in "fiu":
@@ -308,8 +310,12 @@ class Session:
             raise ValueError(f"b must have shape ({self.problem.m},), not {b.shape}")
         b = np.ascontiguousarray(b, dtype=np.float64)
         ms = C.c_double()
-        L.check(L.lib().dlp_session_set_rhs(self._h, _dptr(b), b.shape[0], C.byref(ms)),
-                "dlp_session_set_rhs")
+        if in_place:
+            L.check(L.lib().dlp_session_set_rhs_in_place(self._h, _dptr(b), b.shape[0], C.byref(ms)),
+                    "dlp_session_set_rhs_in_place")
+        else:
+            L.check(L.lib().dlp_session_set_rhs(self._h, _dptr(b), b.shape[0], C.byref(ms)),
+                    "dlp_session_set_rhs")
         return ms.value
 
     def set_defer(self, defer: int, condensed: int = 0, lookahead: int = -1) -> float:

@@ -347,8 +347,8 @@ int dlp_session_step_update(dlp_session* s);
  * created with nranks > 1 or an RCCL id; DLP_ERR_STATE: a failed session, a caller-driven step
  * in progress (step_candidate done, step_update not yet), or a dual phase that is pending or
  * ended DLP_INFEASIBLE (dlp_session_set_rhs: the RHS has negative entries).
- * Not covered: changes of A (changes of b: dlp_session_set_rhs below, eager sessions only;
- * dlp_session_set_defer moves a live deferred session there and back), a
+ * Not covered: changes of A (changes of b: dlp_session_set_rhs below for eager sessions,
+ * dlp_session_set_rhs_in_place for every storage path), a
  * device-pointer c, multi-rank sessions, general LPs.  (Batches: dlp_batch_resolve applies this
  * rule to every resident LP.) */
 int dlp_session_set_objective(dlp_session* s, const double* c, int64_t n, double* kernel_ms);
@@ -389,7 +389,7 @@ int dlp_session_set_objective(dlp_session* s, const double* c, int64_t n, double
  *   1. DLP_ERR_ARG: s or b NULL, m differs from the problem's m, a b_i that is not finite;
  *   2. DLP_ERR_UNSUPPORTED (text in dlp_last_error): a general or MPS problem; a session created
  *      with nranks > 1 or an RCCL id; a deferred session (defer > 1, full or condensed, with or
- *      without lookahead): create the session with defer = 1;
+ *      without lookahead): call dlp_session_set_rhs_in_place, or create the session with defer = 1;
  *   3. DLP_ERR_STATE: a failed session; a caller-driven step in progress; a tableau that is not
  *      dual feasible, some nonbasic z_j < -tol_dj (a session stopped inside a primal solve, or an
  *      unbounded one).
@@ -402,15 +402,44 @@ int dlp_session_set_objective(dlp_session* s, const double* c, int64_t n, double
  *   unbounded call.  dlp_session_result reads x, y and the basis from the tableau as it stands, for
  *   every status.  A negative pivot leaves -0 where a +0 stood in the basic columns of the pivot row;
  *   no comparison of the rule sees the sign of a zero.
- * Not covered: deferred sessions (their replay state and RHS cache would have to be re-established
- * after the eager dual pivots; dlp_session_set_defer(s, 1, ...) below moves a live deferred session
- * to the eager path first and back afterwards), changes of A, a device-pointer b, multi-rank
- * sessions, general LPs. */
+ * Not covered by this call: deferred sessions (dlp_session_set_rhs_in_place below accepts them and
+ * runs the dual phase on their own path; dlp_session_set_defer(s, 1, ...) moves a live deferred
+ * session to the eager path and back), changes of A, a device-pointer b, multi-rank sessions,
+ * general LPs. */
 int dlp_session_set_rhs(dlp_session* s, const double* b, int64_t m, double* kernel_ms);
+/* dlp_session_set_rhs for every storage path: the dual phase runs on the path the session is on
+ * (DESIGN.md §24).  On an eager or small-LP session it is dlp_session_set_rhs itself: the same
+ * code, the same results.  A deferred session (defer = 2..64, full or condensed) is accepted: the
+ * call rebuilds the RHS column by the rule above (on the condensed layout over the stored slots:
+ * the coefficient of slack n+l in row r is T[r][slot] when the slack is nonbasic, 1.0 when it is
+ * basis[r], else +0.0, whose term cannot change a bit and is skipped), resets the Bland state and
+ * sets the status DLP_RUNNING; dlp_session_run then does dual pivots in blocks of `defer`, one
+ * tableau pass per block through the session's pass kernels, and ends DLP_OK, DLP_INFEASIBLE,
+ * DLP_PIVOT_LIMIT or DLP_RUNNING exactly as above ("no eligible row" comes before every budget
+ * test).  Every result is the one the route set_defer(1), set_rhs, run, set_defer back gives: status,
+ * pivot count, log, basis, x, y and objective bit for bit, the tableau read-out byte for byte on
+ * the full layout and up to the sign of a zero in a basic variable's column on the condensed one;
+ * nothing depends on defer, the pass form, the row band, check_interval, use_graph or the budgets.
+ *   Lookahead: a session with lookahead on is accepted; the call drains the lookahead and turns it
+ *     off (as the step API does), dlp_session_get_lookahead then reports 0.  Turn it on again with
+ *     dlp_session_set_defer(s, K, condensed, 1) once the dual phase has ended DLP_OK.
+ *   On the condensed layout the entering ratio's ties go to the smaller variable index (never the
+ *     slot); the RHS slot and the padding are never candidates; dual feasibility is checked per
+ *     stored slot (every stored slot holds a nonbasic variable).
+ * Errors: dlp_session_set_rhs's, in its order, without the "deferred session" refusal; each leaves
+ * the session bit for bit as it was.  The state rules around the phase are those above: while it
+ * is pending or ended DLP_INFEASIBLE, dlp_session_set_objective, _step_* and _set_defer return
+ * DLP_ERR_STATE and both set_rhs calls are accepted again; after DLP_OK the session is an ordinary
+ * optimal deferred session (set_objective, a primal run, another set_rhs_in_place and set_defer
+ * work).  A dual phase starts and ends on an applied block.
+ * Not covered: a dual block beside a lookahead pass, multi-rank and general-LP sessions, a
+ * device-pointer b. */
+int dlp_session_set_rhs_in_place(dlp_session* s, const double* b, int64_t m, double* kernel_ms);
 /* Move a live single-GPU session to another storage path, between runs: the eager
  * full layout (defer = 1), or a deferred one with `defer` pivots per tableau pass, full or
  * condensed, with or without lookahead.  A session can so solve cold on the deferred path, switch
- * to eager for dlp_session_set_rhs and its dual phase, and switch back; or change K between phases.
+ * to eager for dlp_session_set_rhs and its dual phase, and switch back (dlp_session_set_rhs_in_place
+ * runs that dual phase without the switch); or change K between phases.
  *   defer      1 = eager, 2..64 = pivots per pass, 0 = auto: creation's size rule for this tableau;
  *   condensed  -1 / 0 / 1 as dlp_options.condensed (DLP_CONDENSED overrides the auto choice);
  *              ignored when the target is eager;
@@ -447,7 +476,7 @@ int dlp_session_set_rhs(dlp_session* s, const double* b, int64_t m, double* kern
  *      pending or ended DLP_INFEASIBLE (the RHS has negative entries, which no deferred primal path
  *      may see);
  *   4. DLP_ERR_OOM: the new buffers do not fit; they are allocated before anything is changed.
- * Not covered: a deferred dual pivot, multi-rank and general-LP sessions. */
+ * Not covered: multi-rank and general-LP sessions.  (A deferred dual pivot: dlp_session_set_rhs_in_place.) */
 int dlp_session_set_defer(dlp_session* s, int defer, int condensed, int lookahead, double* kernel_ms);
 int dlp_session_buffer(dlp_session* s, int which, void** dev_ptr, size_t* bytes);
 /* Synchronous host copies of an exchange buffer (for host-side communicators). */
@@ -754,8 +783,8 @@ int dlp_batch_resolve(dlp_batch* batch, const double* c, int64_t stridec, int c_
  *   DLP_BATCH_RHS_LDS=1 in the environment, the LDS kernel.  Both give the same bits;
  *   dlp_batch_rhs_kernel says which one runs.
  * Not covered: changes of A, c and b in one call, general LPs.  (Single sessions:
- * dlp_session_set_rhs applies this rule to an eager session's tableau; deferred sessions remain
- * the gap.) */
+ * dlp_session_set_rhs applies this rule to an eager session's tableau, dlp_session_set_rhs_in_place
+ * to a session on any storage path.) */
 int dlp_batch_resolve_rhs(dlp_batch* batch, const double* b, int64_t strideb, int b_is_device,
                           int64_t max_pivots, const dlp_batch_out* out);
 /* The kernel dlp_batch_resolve_rhs runs for this batch: *register_kernel 1 the register-resident
