@@ -53,16 +53,29 @@ __device__ inline void stv(double* p, d2 v) {
 // waits of their own (vmwait), which hold because between two of them they issue no other
 // vector-memory instruction, or a fixed number of them.  The lgkmcnt(0) orders the DMA's
 // LDS write after this wave's earlier LDS reads of the slot it refills.
+// NTL: the DMA carries the nt cache policy (a single-use stream: it leaves the re-read data of the
+// kernels beside it in the caches; profiles/r04s lab8).  Only the asm string differs.
+template <bool NTL = false>
 __device__ __forceinline__ void glds16(const void* g, uint32_t m0) {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "{m0}"(m0) : "memory");
+    if constexpr (NTL)
+        asm volatile("s_waitcnt lgkmcnt(0)\n\tglobal_load_lds_dwordx4 %0, off nt" ::"v"(g), "{m0}"(m0) : "memory");
+    else
+        asm volatile("s_waitcnt lgkmcnt(0)\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "{m0}"(m0) : "memory");
 }
 // The same DMA in the scalar-base form: lane x reads 16 B at base + voff (voff: unsigned 32-bit bytes),
 // the wave-uniform base in an SGPR pair, so a stream that only advances by a uniform stride needs no
 // per-lane address arithmetic.  The s_nop covers a base that an SALU add has just written (the
 // compiler pads nothing inside the statement).
+template <bool NTL = false>
 __device__ __forceinline__ void glds16s(uint32_t voff, const void* base, uint32_t m0) {
-    asm volatile("s_nop 4\n\ts_waitcnt lgkmcnt(0)\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "{m0}"(m0)
-                 : "memory");
+    if constexpr (NTL)
+        asm volatile("s_nop 4\n\ts_waitcnt lgkmcnt(0)\n\tglobal_load_lds_dwordx4 %0, %1 nt" ::"v"(voff), "s"(base),
+                     "{m0}"(m0)
+                     : "memory");
+    else
+        asm volatile("s_nop 4\n\ts_waitcnt lgkmcnt(0)\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base),
+                     "{m0}"(m0)
+                     : "memory");
 }
 template <int N>
 __device__ __forceinline__ void vmwait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }

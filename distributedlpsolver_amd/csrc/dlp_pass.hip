@@ -1111,8 +1111,12 @@ __device__ __forceinline__ double redo_pivot_row(const double* cr, int cl, const
 // rows; the same barrier says that every wave is done with supergroup sg - 1, whose slot is refilled
 // behind it.  A bare s_barrier: __syncthreads() would drain the ring and the stores.  Every wave of a
 // workgroup runs the same ng groups on every path, so the barriers match.
+// NL (with NT): the tableau DMAs carry the nt policy (DLP_PASS_NTLOAD): the tableau is read once per
+// pass, and a default-policy stream of its size evicts what the chain beside the pass and the pass
+// itself re-read (C, P, cls, nzc: those loads, and the coefficient DMAs, keep the default policy).
+// Only the asm string differs: the DMAs per group, and with them the counted waits, stay.
 // (three waves per SIMD, at most 168 VGPRs, as before the pivot-row recompute was added)
-template <bool NT, int U, int D, bool SA = false, bool CS = false, bool PUB = false>
+template <bool NT, int U, int D, bool SA = false, bool CS = false, bool NL = false, bool PUB = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void pass_q_kernel(
                                                      const double* __restrict__ T, double* __restrict__ Tout,
                                                      int64_t ld, int64_t rows, int64_t width,
@@ -1185,11 +1189,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void p
                 const int rk = gg * U + 2 * k;
                 const bool pair = rk + 1 < nr;   // (uniform)
                 const uint32_t up = lane >> 5 ? (uint32_t)(ld * 8) : 0u;
-                glds16s(pair ? tvoff : tvoff - up, T + (i0 + (rk < nr ? rk : nr - 1)) * ld, m0);
+                glds16s<NL>(pair ? tvoff : tvoff - up, T + (i0 + (rk < nr ? rk : nr - 1)) * ld, m0);
             } else {
                 int r = gg * U + 2 * k + (lane >> 5);
                 r = r < nr ? r : nr - 1;
-                glds16(tsrc + (int64_t)r * ld, m0);
+                glds16<NL>(tsrc + (int64_t)r * ld, m0);
             }
         }
         if constexpr (CS) return;
@@ -1214,7 +1218,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void p
     auto dma_s = [&](int s) {
 #pragma unroll
         for (int k = 0; k < U / 2; ++k)
-            glds16s(tvoff, tb + (int64_t)2 * k * ld * 8,
+            glds16s<NL>(tvoff, tb + (int64_t)2 * k * ld * 8,
                     __builtin_amdgcn_readfirstlane(lbase + s * SLOT * 8 + k * 1024));
         if constexpr (CS) return;
 #pragma unroll
@@ -1664,14 +1668,40 @@ static size_t pass_q_lds(int U, int D, bool shared) {
     return shared ? ((size_t)4 * D + kCsNS * kCsG) * 64 * U * sizeof(double) : (size_t)4 * D * 128 * U * sizeof(double);
 }
 
+// DLP_PASS_NTLOAD (A/B): 1 / 0: the form-23 pass's tableau DMAs with the nt policy wherever such an
+// instance exists (and the session is nontemporal) / nowhere; unset: the shipped choice
+static int pass_ntload_env() {
+    static const int v = env_int("DLP_PASS_NTLOAD", -1);
+    return v;
+}
+// The shipped choice: on at every geometry (C3: the pass 39 us shorter, the chain kernels beside it 1.1-1.3 us
+// each, the bench line +1.8% against the parent in four alternating pairs; c3r2 +2.1 / +2.6%, c3r4 +0.8 / +2.6%);
+// DESIGN.md 16.5, profiles/c3_pass_ntload/
+constexpr bool kPassNtloadDefault = true;
+// The nt DMAs are compiled for the instances the auto policy picks on a streaming tableau: (U, D) = (4, 2)
+// and (2, 4), scalar-base or per-lane, and with the shared coefficient ring where it is the shipped choice
+constexpr bool pass_q_ntload_exists(bool NT, int U, int D, bool cs) {
+    return NT && ((U == 4 && D == 2) || (U == 2 && D == 4 && !cs));
+}
+
 // The form-23 instance of (U, D): scalar-base DMAs or per-lane ones (sad), the shared coefficient ring
-// (csh; with sad), publishing or not (bcnt)
+// (csh; with sad), publishing or not (bcnt); the nt tableau DMAs where asked for and compiled
 template <bool NT, int U, int D>
 static void launch_pass_q(const Geometry& g, const Defer& d, const BlockDesc* bd, double* To, int rb,
                           uint32_t* bcnt, bool sad, bool csh, int pivg, dim3 grid, size_t dyn, hipStream_t s) {
+    const int nle = pass_ntload_env();
+    const bool ntl = nle >= 0 ? nle != 0 : kPassNtloadDefault;
     auto go = [&](auto sa, auto cs, auto pub) {
-        pass_q_kernel<NT, U, D, decltype(sa)::value, decltype(cs)::value, decltype(pub)::value>
-            <<<grid, 256, dyn, s>>>(g.T, To, g.ld, g.rows, g.width, bd, d.C, d.ldc, d.P, d.nzc, rb, bcnt, pivg);
+        constexpr bool SA = decltype(sa)::value, CS = decltype(cs)::value, PUB = decltype(pub)::value;
+        if constexpr (pass_q_ntload_exists(NT, U, D, CS)) {
+            if (ntl) {
+                pass_q_kernel<NT, U, D, SA, CS, true, PUB><<<grid, 256, dyn, s>>>(
+                    g.T, To, g.ld, g.rows, g.width, bd, d.C, d.ldc, d.P, d.nzc, rb, bcnt, pivg);
+                return;
+            }
+        }
+        pass_q_kernel<NT, U, D, SA, CS, false, PUB><<<grid, 256, dyn, s>>>(
+            g.T, To, g.ld, g.rows, g.width, bd, d.C, d.ldc, d.P, d.nzc, rb, bcnt, pivg);
     };
     constexpr std::true_type yes{};
     constexpr std::false_type no{};

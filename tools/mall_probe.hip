@@ -10,6 +10,10 @@
 // 16 sc1, 17 sc0 sc1, 18 nt sc1, 3 sc0 nt, 19 sc0 nt sc1): read the table (warm), stream-copy
 // stream_MB through that policy, then time one read of the table.  A table still in the MALL reads
 // at the "no stream" rate; an evicted one at the HBM rate.
+// The "dma" rows stream as the form-23 pass does: reads by LDS-DMA (global_load_lds_dwordx4, default
+// policy or nt) into a per-wave ring retired by counted vmcnt waits, stores by buffer ops (default or nt).
+//   latency mode: tools/bin/mall_probe table_MB stream_MB workgroups 1 [kind]
+//   kind of the stream beside the chase: 0 buffer nt (default), 1 dma default + nt stores, 2 dma nt + nt stores
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -58,6 +62,68 @@ __global__ __launch_bounds__(256) void stream_kernel(const double* __restrict__ 
     }
 }
 
+// The same copy with LDS-DMA reads: each wave keeps R 1-KiB DMAs in flight into its ring (lane x's
+// 16 B land at slot + 16 x), waits for the oldest by count, reads its 16 B back and stores them.
+// Every iteration issues exactly one store and one DMA (a refill past the wave's last chunk re-reads
+// that chunk), so newer than iteration k's DMA are R - 1 + k operations in the first R - 1 iterations
+// and 2 (R - 1) from then on.  bytes: a multiple of 1 KiB.
+template <int N>
+__device__ __forceinline__ void vmwait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+template <bool NTL>
+__device__ __forceinline__ void glds16(const void* g, uint32_t m0) {
+    if constexpr (NTL)
+        asm volatile("s_waitcnt lgkmcnt(0)\n\tglobal_load_lds_dwordx4 %0, off nt" ::"v"(g), "{m0}"(m0) : "memory");
+    else
+        asm volatile("s_waitcnt lgkmcnt(0)\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "{m0}"(m0) : "memory");
+}
+constexpr int kDmaRing = 8;
+template <bool NTL, int AUX>
+__global__ __launch_bounds__(256) void dma_stream_kernel(const double* __restrict__ src, double* __restrict__ dst,
+                                                         size_t bytes) {
+    constexpr int R = kDmaRing;
+    extern __shared__ double ring[];   // [4 waves][R][128]
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const double* wring = ring + (size_t)w * R * 128;
+    const uint32_t lbase = __builtin_amdgcn_readfirstlane(
+        (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)wring);
+    const size_t win = (size_t)1 << 30;
+    for (size_t w0 = 0; w0 < bytes; w0 += win) {
+        const uint32_t wb = (uint32_t)std::min(win, bytes - w0);
+        const __amdgpu_buffer_rsrc_t rd = rsrc((char*)dst + w0, wb);
+        const uint32_t nch = wb >> 10, gw = blockIdx.x * 4u + w, stride = gridDim.x * 4u;
+        if (gw >= nch) continue;   // (uniform per wave)
+        const int n = (int)((nch - gw + stride - 1) / stride);   // this wave's chunks gw + k stride, k < n
+        const char* s0 = (const char*)src + w0 + lane * 16;
+        auto issue = [&](int k) {
+            const uint32_t c = gw + (uint32_t)(k < n ? k : n - 1) * stride;   // < nch
+            glds16<NTL>(s0 + (size_t)c * 1024, __builtin_amdgcn_readfirstlane(lbase + (k % R) * 1024));
+        };
+#pragma unroll
+        for (int k = 0; k < R; ++k) issue(k);
+        for (int k = 0; k < n; ++k) {
+            if (k >= R - 1) {
+                vmwait<2 * (R - 1)>();
+            } else {
+                switch (k) {
+                    case 0: vmwait<R - 1>(); break;
+                    case 1: vmwait<R>(); break;
+                    case 2: vmwait<R + 1>(); break;
+                    case 3: vmwait<R + 2>(); break;
+                    case 4: vmwait<R + 3>(); break;
+                    case 5: vmwait<R + 4>(); break;
+                    default: vmwait<R + 5>(); break;
+                }
+            }
+            const d2 v = *(const d2*)(wring + (k % R) * 128 + 2 * lane);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v),
+                                                   rd, (gw + (uint32_t)k * stride) * 1024u + lane * 16u, 0, AUX);
+            issue(k + R);
+        }
+        vmwait<0>();
+    }
+}
+
 // latency: one wave, lane 0 follows a chain of dependent loads: a random cycle over every 128-B line
 // of the table, continued from where the previous launch stopped (state[1]), so each launch meets
 // lines last touched a whole table ago: out of the 4 MiB L2, in the Infinity Cache
@@ -76,6 +142,11 @@ typedef void (*StreamFn)(const double*, double*, size_t);
 template <int AUX>
 void launch_stream(const double* s, double* d, size_t bytes) {
     stream_kernel<AUX><<<256 * 8, 256>>>(s, d, bytes);
+}
+
+template <bool NTL, int AUX>
+void launch_dma_stream(const double* s, double* d, size_t bytes) {
+    dma_stream_kernel<NTL, AUX><<<256 * 8, 256, 4 * kDmaRing * 1024>>>(s, d, bytes);
 }
 
 int main(int argc, char** argv) {
@@ -112,7 +183,10 @@ int main(int argc, char** argv) {
                       {16, "sc1", launch_stream<16>},
                       {17, "sc0 sc1", launch_stream<17>},
                       {18, "nt sc1", launch_stream<18>},
-                      {19, "sc0 nt sc1", launch_stream<19>}};
+                      {19, "sc0 nt sc1", launch_stream<19>},
+                      {0, "dma/st dflt", launch_dma_stream<false, 0>},
+                      {2, "dma dflt/st nt", launch_dma_stream<false, 2>},
+                      {2, "dma nt/st nt", launch_dma_stream<true, 2>}};
     if (argc > 4) {   // latency: dependent loads beside an nt stream of argv[3] workgroups
         const int nwg = std::atoi(argv[3]);
         const size_t nq = tb / 8, nl = tb / 128;
@@ -138,12 +212,20 @@ int main(int argc, char** argv) {
         CK(hipStreamCreateWithPriority(&sa, hipStreamNonBlocking, lo));
         CK(hipStreamCreateWithPriority(&sbq, hipStreamNonBlocking, hi));
         const int hops = 2000;
+        const int kind = argc > 5 ? std::atoi(argv[5]) : 0;
+        const char* kname = kind == 1 ? "a default-policy dma" : kind == 2 ? "an nt dma" : "an nt";
         for (int rep = 0; rep < 4; ++rep) {
             for (int w = 0; w < 300; ++w)   // warm: the whole cycle, twice
                 chase_kernel<<<1, 64, 0, sbq>>>((const uint64_t*)table, hops, (uint64_t*)out, cyc);
             CK(hipDeviceSynchronize());
-            for (int r = 0; nwg > 0 && r < 12; ++r)   // ~40 ms of stream: every chase below runs beside it
-                stream_kernel<2><<<nwg, 256, 0, sa>>>(src, dst, sb);
+            for (int r = 0; nwg > 0 && r < 12; ++r) {   // ~40 ms of stream: every chase below runs beside it
+                if (kind == 1)
+                    dma_stream_kernel<false, 2><<<nwg, 256, 4 * kDmaRing * 1024, sa>>>(src, dst, sb);
+                else if (kind == 2)
+                    dma_stream_kernel<true, 2><<<nwg, 256, 4 * kDmaRing * 1024, sa>>>(src, dst, sb);
+                else
+                    stream_kernel<2><<<nwg, 256, 0, sa>>>(src, dst, sb);
+            }
             std::vector<double> ns;
             for (int k = 0; k < 10; ++k) {
                 chase_kernel<<<1, 64, 0, sbq>>>((const uint64_t*)table, hops, (uint64_t*)out, cyc);
@@ -154,8 +236,8 @@ int main(int argc, char** argv) {
             }
             CK(hipDeviceSynchronize());
             std::sort(ns.begin(), ns.end());
-            std::printf("dependent-load latency beside an nt stream of %4d workgroups: median %.0f ns per hop (min %.0f)\n",
-                        nwg, ns[5], ns[0]);
+            std::printf("dependent-load latency beside %s stream of %4d workgroups: median %.0f ns per hop (min %.0f)\n",
+                        kname, nwg, ns[5], ns[0]);
             std::fflush(stdout);
         }
         return 0;
@@ -212,7 +294,7 @@ int main(int argc, char** argv) {
                 t.push_back(read_ms());
             }
             std::sort(t.begin(), t.end());
-            std::printf("%-12s stream %7.3f ms (%5.0f GB/s)   table read after: median %.4f ms = %6.0f GB/s\n", p.name,
+            std::printf("%-14s stream %7.3f ms (%5.0f GB/s)   table read after: median %.4f ms = %6.0f GB/s\n", p.name,
                         st_ms, p.fn ? 2.0 * sb / st_ms / 1e6 : 0.0, t[2], tb / t[2] / 1e6);
             std::fflush(stdout);
         }
