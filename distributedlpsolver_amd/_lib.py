@@ -224,6 +224,8 @@ SIGNATURES = [
      [_I64, _I64, _I64, C.POINTER(BatchDenseIn), C.POINTER(Options), C.POINTER(BatchOut), C.POINTER(_P)]),
     ("dlp_batch_resolve", C.c_int, [_P, C.c_void_p, _I64, C.c_int, _I64, C.POINTER(BatchOut)]),
     ("dlp_batch_resolve_rhs", C.c_int, [_P, C.c_void_p, _I64, C.c_int, _I64, C.POINTER(BatchOut)]),
+    ("dlp_batch_add_rows", C.c_int,
+     [_P, _I64, C.c_void_p, _I64, C.c_void_p, _I64, C.c_int, _I64, C.POINTER(BatchOut)]),
     ("dlp_batch_read", C.c_int, [_P, _I64, _DP, C.POINTER(_I32)]),
     ("dlp_batch_info", C.c_int,
      [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_I64)]),

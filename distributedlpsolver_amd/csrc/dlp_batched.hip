@@ -97,12 +97,12 @@ struct BatchOut {
 // condensed tableau: slot j of row i is A_k[i][j], the RHS b_k[i], the objective row -c_k[j]
 // with value +0 (the single-LP dense fill), and no full-layout copy passes through HBM.
 struct GenIn {
-    static constexpr bool dense = false, resident = false, keep = false, dual = false;
+    static constexpr bool dense = false, resident = false, keep = false, dual = false, grow = false;
     const double* T;
     int64_t ld;
 };
 struct DenseIn {
-    static constexpr bool dense = true, resident = false, keep = false, dual = false;
+    static constexpr bool dense = true, resident = false, keep = false, dual = false, grow = false;
     const double *A, *b, *c;
     int64_t sA, sb, sc;
 };
@@ -128,7 +128,7 @@ struct DenseKeepIn : DenseIn {
     BatchState st;
 };
 struct ResIn {
-    static constexpr bool dense = false, resident = true, keep = true, dual = false;
+    static constexpr bool dense = false, resident = true, keep = true, dual = false, grow = false;
     BatchState st;
     const double* c;
     int64_t sc;
@@ -137,12 +137,30 @@ struct ResIn {
 // (dlp_batch_resolve_rhs): the prologue rebuilds LP k's RHS column from
 // b + k * sb by the fold of dlp.h, then the pivot loop selects the leaving row first.
 struct RhsIn {
-    static constexpr bool dense = false, resident = true, keep = true, dual = true;
+    static constexpr bool dense = false, resident = true, keep = true, dual = true, grow = false;
     BatchState st;
     const double* b;
     int64_t sb;
     double tol_feas;
     double* last;   // [nlp * m]: the b_k each LP's RHS column was last built from (continuation, below)
+    static constexpr const double* c = nullptr;   // (no new objective in this call)
+    static constexpr int64_t sc = 0;
+};
+// AddIn: the resident state grown by r constraint rows per LP and continued by the dual simplex
+// (dlp_batch_add_rows).  The kernel's m is the grown row count; the prologue reads
+// LP k's record of m - r rows at src (row stride W unchanged, the objective row to row m), folds
+// the r new rows G_k x <= h_k into the current basis by the row rule of dlp.h and stores the record
+// of the grown shape at st.  r == 0: src is st.S itself, nothing is folded, `last` is not touched.
+struct AddIn {
+    static constexpr bool dense = false, resident = true, keep = true, dual = true, grow = true;
+    BatchState st;
+    const double* src;
+    int r;
+    const double *G, *h;   // LP k: r x n row-major at G + k * sG, r doubles at h + k * sh
+    int64_t sG, sh;
+    double tol_feas;
+    double* last;    // [nlp * m] of the grown shape, filled with NaN: no finite b_k continues it
+    int32_t* flag;   // the smallest LP index with a G_k / h_k entry that is not finite (atomicMin)
     static constexpr const double* c = nullptr;   // (no new objective in this call)
     static constexpr int64_t sc = 0;
 };
@@ -155,6 +173,12 @@ __device__ __forceinline__ double fold_step(double acc, double cb, double t) {
 #pragma clang fp contract(off)
     const double prod = cb * t;
     return acc + prod;
+}
+// acc = acc - (gb * t): the row rule's step of dlp_batch_add_rows, v_mul_f64 then v_add_f64
+__device__ __forceinline__ double unfold_step(double acc, double gb, double t) {
+#pragma clang fp contract(off)
+    const double prod = gb * t;
+    return acc - prod;
 }
 typedef unsigned int u32x2 __attribute__((__vector_size__(2 * sizeof(unsigned int))));   // a b64 buffer store's data
 __device__ __forceinline__ double mul_rounded(double a, double b) {
@@ -212,14 +236,49 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
                 di[N] = sI[4];
                 di[N + 1] = stt;
             }
-            if constexpr (In::dual) {   // the b_k this RHS column was built from
+            if constexpr (In::grow) {   // no finite b_k matches the grown record: a later resolve_rhs rebuilds
+                if (in.r > 0)
+                    for (int i = tid; i < m; i += blockDim.x) in.last[lp * m + i] = __builtin_nan("");
+            } else if constexpr (In::dual) {   // the b_k this RHS column was built from
                 const double* __restrict__ b = in.b + lp * in.sb;
                 for (int i = tid; i < m; i += blockDim.x) in.last[lp * m + i] = b[i];
             }
         }
     };
     bool has_c = false;   // (resident) a new objective: the rows are read by the fold below
-    if constexpr (In::resident) {
+    if constexpr (In::grow) {
+        // The record of m - r rows: its constraint rows keep their place (the stride W is the
+        // grown shape's too), its objective row moves to row m, the new slacks are basic in
+        // their own rows.  sF borrows sD (next written after the pivot loop's first barrier):
+        // [0] a G_k / h_k entry that is not finite, [1] a refused LP's new RHS below -tol_feas.
+        const int r = in.r, mo = m - r, No = n + mo;
+        const double* __restrict__ src = in.src + lp * state_doubles(mo, n);
+        const int32_t* __restrict__ si = (const int32_t*)(src + (mo + 1) * W);
+        int32_t* sF = (int32_t*)sD;
+        for (int s = tid; s < n; s += blockDim.x) var[s] = si[s];
+        for (int i = tid; i < mo; i += blockDim.x) basis[i] = si[n + i];
+        for (int t = tid; t < r; t += blockDim.x) basis[mo + t] = No + t;
+        for (int e = tid; e < mo * W; e += blockDim.x) T[e] = src[e];
+        for (int s = tid; s < W; s += blockDim.x) T[m * W + s] = src[mo * W + s];
+        if (wid == 0) {
+            // 1: rejected at creation; 3: some stored slot has z < -tol_dj (not dual feasible)
+            const int sv = si[No + 1];
+            int bad = sv == DLP_ERR_ARG ? 1 : 0;
+            bool neg = false;
+            for (int s = lane; s < n; s += 64) neg |= src[mo * W + s] < -tol_dj;
+            if (__ballot(neg) != 0 && bad == 0) bad = 3;
+            if (lane == 0) {
+                // r == 0 continues a pending dual phase with its Bland state; a refused LP keeps
+                // its stored status and Bland state in the grown record
+                const bool cont = r == 0 && sv == kDualPending;
+                sI[5] = bad;
+                sI[3] = bad ? sv : (int)DLP_RUNNING;
+                sI[4] = bad ? si[No] : ((cont && si[No]) || pricing == DLP_PRICING_BLAND ? 1 : 0);
+                sF[0] = 0;
+                sF[1] = 0;
+            }
+        }
+    } else if constexpr (In::resident) {
         const double* __restrict__ src = in.st.S + lp * state_doubles(m, n);
         const int32_t* __restrict__ si = (const int32_t*)(src + (m + 1) * W);
         has_c = !In::dual && in.c != nullptr;
@@ -304,6 +363,65 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
         }
     }
     __syncthreads();
+    if constexpr (In::grow) {
+        if (in.r > 0) {
+            // The row rule (dlp.h, dlp_batch_add_rows): new row t in the current basis is
+            // g - sum_i gB_i * T[i] over the old rows ascending, gB_i = g[basis[i]] (a slack: +0.0),
+            // rows with gB_i == 0.0 skipped, the product rounded, then the difference.  One work
+            // item owns one slot of one new row; gB is staged where the entering column and the
+            // pivot row will live, as many new rows at a time as fit there.  It holds for any
+            // basis, so rejected and refused LPs take it too.
+            const int r = in.r, mo = m - r;
+            const double* __restrict__ G = in.G + lp * in.sG;
+            const double* __restrict__ h = in.h + lp * in.sh;
+            int32_t* sF = (int32_t*)sD;
+            bool nf = false;
+            for (int e = tid; e < r * n; e += blockDim.x) nf |= not_finite(G[e]);
+            for (int t = tid; t < r; t += blockDim.x) nf |= not_finite(h[t]);
+            if (__ballot(nf) != 0 && lane == 0) {
+                atomicMin(in.flag, (int32_t)lp);
+                sF[0] = 1;
+            }
+            double* gB = colq;
+            const int ch = min(r, (m + 1 + W) / mo);   // >= 1: m + 1 > mo
+            for (int t0 = 0; t0 < r; t0 += ch) {
+                const int tc = min(ch, r - t0);
+                for (int e = tid; e < tc * mo; e += blockDim.x) {
+                    const int t = e / mo, i = e - t * mo;
+                    const int bv = basis[i];
+                    gB[e] = bv < n ? G[(int64_t)(t0 + t) * n + bv] : 0.0;
+                }
+                __syncthreads();
+                for (int item = tid; item < tc * W; item += blockDim.x) {
+                    const int t = item / W, s = item - t * W;
+                    const double* gb = gB + t * mo;
+                    double acc = 0.0;
+                    if (s == n) acc = h[t0 + t];
+                    else if (var[s] < n) acc = G[(int64_t)(t0 + t) * n + var[s]];
+                    for (int i0 = 0; i0 < mo; i0 += 8) {   // loads first, then the dependent chain
+                        double tt[8], f[8];
+#pragma unroll
+                        for (int u = 0; u < 8; ++u) {
+                            const int i = min(i0 + u, mo - 1);
+                            f[u] = gb[i];
+                            tt[u] = T[i * W + s];
+                        }
+#pragma unroll
+                        for (int u = 0; u < 8; ++u)
+                            if (i0 + u < mo && f[u] != 0.0) acc = unfold_step(acc, f[u], tt[u]);
+                    }
+                    T[(mo + t0 + t) * W + s] = acc;
+                }
+                __syncthreads();
+            }
+            if (sI[5] == 3) {   // (uniform) refused: does a new row make the record primal infeasible?
+                for (int t = tid; t < r; t += blockDim.x)
+                    if (T[(mo + t) * W + n] < -in.tol_feas) sF[1] = 1;
+                __syncthreads();
+            }
+            if (sF[0]) return;   // (uniform) the call fails as a whole: nothing of it is kept
+        }
+    }
     if constexpr (In::dense || In::resident) {
         if (sI[5]) {   // (uniform) DLP_ERR_ARG, no pivots, the slack basis, NaN values
             const double nan = __builtin_nan("");
@@ -323,6 +441,10 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
             // a fresh batch keeps the rejected LP as loaded, marked DLP_ERR_ARG; a resident one
             // is left exactly as it was
             if constexpr (!In::resident) store_state(DLP_ERR_ARG);
+            // a grown one takes the LP's record of the new shape: its stored status and Bland state
+            // (sI[3], sI[4]), or pending when a new row has made it primal infeasible as well
+            if constexpr (In::grow)
+                if (in.r > 0) store_state(sI[5] == 3 && ((const int32_t*)sD)[1] ? kDualPending : sI[3]);
             return;
         }
     }
@@ -355,7 +477,7 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
             __syncthreads();
         }
     }
-    if constexpr (In::dual) if (sI[0] == 0) {   // (uniform; sI[0] is next written after the pivot loop's first barrier)
+    if constexpr (In::dual && !In::grow) if (sI[0] == 0) {   // (uniform; sI[0] is next written after the pivot loop's first barrier)
         // The RHS rebuild (dlp.h, dlp_batch_resolve_rhs's rule): the slack columns of the full
         // layout are B^-1, so row r's new RHS is the fold of Tfull[r][n + l] * b_l over l
         // ascending, one thread per row (the objective row included: its entry is the new
@@ -1550,6 +1672,13 @@ struct BatchJob {
     // dlp_batch_resolve_rhs: vec holds the new right-hand sides (m doubles per LP) and the dual
     // instantiation runs
     bool rhs;
+    // dlp_batch_add_rows: m is the grown row count, r of its rows are new (LP k's r x n at
+    // G + k * sG, its r right-hand sides at h + k * sh; rows_device: device pointers)
+    bool grow;
+    int64_t r;
+    const double *G, *h;
+    int64_t sG, sh;
+    int rows_device;
 };
 
 int batched_run(const dlp_options& o, const BatchJob& job) {
@@ -1592,8 +1721,11 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
         if (lk.owns_lock()) c = &g_batch[o.device];
     }
     uint64_t* dStamps = nullptr;
+    void *newS = nullptr, *newL = nullptr;   // dlp_batch_add_rows: the grown records, swapped in on success
+    bool refused = false;                    // ... a non-finite row: the call fails, the context stays
     dlp::BatchOut bo{};
     const size_t bOut = (sizeof(double) + sizeof(int64_t) + sizeof(int32_t)) * (size_t)nlp;
+    const size_t bFlag = job.grow ? 16 : 0;   // (the device flag of dlp::AddIn behind the packed outputs)
     double* dObj = nullptr;
     int64_t* dNp = nullptr;
     int32_t* dSt = nullptr;
@@ -1610,8 +1742,8 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
     if (!c->e1) HIP_BTRY(hipEventCreate(&c->e1));
     if (!din && !job.resolve) HIP_BTRY(ensure_buf(&c->dT, &c->capT, sizeof(double) * nlp * (m + 1) * ldg));
     if (stage) HIP_BTRY(ensure_buf(&c->dIn, &c->capIn, sizeof(double) * (cntA + cntb + cntc)));
-    HIP_BTRY(ensure_buf(&c->dOut, &c->capOut, bOut));
-    HIP_BTRY(ensure_buf(&c->hOut, &c->capH, bOut, true));
+    HIP_BTRY(ensure_buf(&c->dOut, &c->capOut, bOut + bFlag));
+    HIP_BTRY(ensure_buf(&c->hOut, &c->capH, bOut + bFlag, true));
     if (basis) HIP_BTRY(ensure_buf(&c->dB, &c->capB, sizeof(int32_t) * nlp * m));
     if (want_log) HIP_BTRY(ensure_buf(&c->dL, &c->capL, sizeof(dlp_pivot) * nlp * log_cap));
     if (job.out.x) HIP_BTRY(ensure_buf(&c->dX, &c->capX, sizeof(double) * nlp * n));
@@ -1650,7 +1782,48 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
             }
             bt->bytes += (int64_t)bL;
         }
-        if (job.resolve) {
+        dlp::AddIn ain{};
+        if (job.grow) {
+            const int64_t r = job.r;
+            ain.st = bst;
+            ain.src = (const double*)bt->dS;
+            ain.r = (int)r;
+            ain.tol_feas = o.tol_feas;
+            ain.last = (double*)bt->dBlast;
+            if (r > 0) {
+                // the records and the `last` buffer of the grown shape: the kernel fills them, the
+                // handle takes them only when no LP's rows were refused
+                const size_t bS = sizeof(double) * nlp * dlp::state_doubles(m, n), bL = sizeof(double) * nlp * m;
+                if (hipMalloc(&newS, bS) != hipSuccess || hipMalloc(&newL, bL) != hipSuccess) {
+                    (void)hipGetLastError();
+                    dlp::set_error(who + ": the grown state does not fit in device memory");
+                    rc = DLP_ERR_OOM;
+                    goto done;
+                }
+                ain.st = dlp::BatchState{(double*)newS};
+                ain.last = (double*)newL;
+                ain.flag = (int32_t*)((char*)c->dOut + bOut);
+                HIP_BTRY(hipMemsetAsync(ain.flag, 0x7f, sizeof(int32_t), s));   // (above every LP index)
+                if (job.rows_device) {
+                    ain.G = job.G; ain.h = job.h; ain.sG = job.sG; ain.sh = job.sh;
+                } else {   // host rows: packed G | h, a shared array once
+                    const size_t cntG = (size_t)(job.sG ? nlp : 1) * r * n, cnth = (size_t)(job.sh ? nlp : 1) * r;
+                    HIP_BTRY(ensure_buf(&c->dIn, &c->capIn, sizeof(double) * (cntG + cnth)));
+                    auto put = [&](double* dst, const double* src, int64_t per, int64_t stride) {
+                        if (stride == 0 || stride == per)
+                            return hipMemcpyAsync(dst, src, sizeof(double) * per * (stride ? nlp : 1),
+                                                  hipMemcpyHostToDevice, s);
+                        return hipMemcpy2DAsync(dst, sizeof(double) * per, src, sizeof(double) * stride,
+                                                sizeof(double) * per, (size_t)nlp, hipMemcpyHostToDevice, s);
+                    };
+                    double* dG = (double*)c->dIn;
+                    HIP_BTRY(put(dG, job.G, r * n, job.sG));
+                    HIP_BTRY(put(dG + cntG, job.h, r, job.sh));
+                    ain.G = dG; ain.h = dG + cntG;
+                    ain.sG = job.sG ? r * n : 0; ain.sh = job.sh ? r : 0;
+                }
+            }
+        } else if (job.resolve) {
             if (job.vec && !job.vec_device) {   // a host vector: packed into the handle's staging buffer
                 const int64_t cnt = job.rhs ? m : n;   // (right-hand sides: m per LP, their own buffer)
                 const size_t per = sizeof(double) * cnt;
@@ -1718,7 +1891,8 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
         const int nw = (int)((n + 63) / 64);
         // (the dual re-solve runs the register kernel's RhsIn instantiation on the same records;
         // DLP_BATCH_RHS_LDS=1 sends that call alone through the LDS kernel)
-        const bool reg = !force_lds && m == 64 && nw >= 1 && nw <= 3 && !(job.rhs && rhs_force_lds());
+        // (dlp_batch_add_rows always runs the LDS kernel: DESIGN.md §25)
+        const bool reg = !force_lds && m == 64 && nw >= 1 && nw <= 3 && !(job.rhs && rhs_force_lds()) && !job.grow;
         // the kernel of this input kind (its own instantiation, so its own dynamic-LDS attribute),
         // timed alone between e0 and e1
         auto launch = [&](auto in) -> hipError_t {
@@ -1730,6 +1904,7 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
             if (e == hipSuccess) e = hipEventRecord(c->e0, s);
             if (e != hipSuccess) return e;
             if (reg) {
+              if constexpr (!In::grow) {   // (no register-kernel instantiation of the growth source)
                 if (nw == 1)
                     dlp::batched_reg_kernel<64, 1, In><<<(unsigned)nlp, 64, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
                                                                                   o.tol_dj, o.tol_piv, bo);
@@ -1739,6 +1914,7 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
                 else
                     dlp::batched_reg_kernel<64, 3, In><<<(unsigned)nlp, 192, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
                                                                                    o.tol_dj, o.tol_piv, bo);
+              }
             } else {
                 // 512 lanes per LP when few LPs share a CU (LDS > 40 KB each), else 256
                 const unsigned threads = lds > 40 * 1024 ? 512 : 256;
@@ -1747,7 +1923,9 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
             }
             return hipGetLastError();
         };
-        if (job.rhs)
+        if (job.grow)
+            HIP_BTRY(launch(ain));
+        else if (job.rhs)
             HIP_BTRY(launch(dlp::RhsIn{bst, dvec, dstride, o.tol_feas, (double*)bt->dBlast}));
         else if (job.resolve)
             HIP_BTRY(launch(dlp::ResIn{bst, dvec, dstride}));
@@ -1755,8 +1933,40 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
             HIP_BTRY(launch(dlp::DenseKeepIn{dn, bst}));
         else
             HIP_BTRY(din ? launch(dn) : launch(gin));
-        if (bt && !job.rhs) bt->reg = reg;   // (the kernel of creation and of dlp_batch_resolve)
+        if (bt && !job.rhs && !job.grow) bt->reg = reg;   // (the kernel of creation and of dlp_batch_resolve)
         HIP_BTRY(hipEventRecord(c->e1, s));
+        if (job.grow && job.r > 0) {
+            // all or nothing: a non-finite row in any LP leaves the batch and `out` as they were
+            int32_t* const hflag = (int32_t*)((char*)c->hOut + bOut);
+            HIP_BTRY(hipMemcpyAsync(hflag, ain.flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            HIP_BTRY(hipStreamSynchronize(s));
+            if (*hflag >= 0 && *hflag < nlp) {
+                dlp::set_error(who + ": LP " + std::to_string(*hflag) + ": a G or h entry is not finite");
+                refused = true;
+                rc = DLP_ERR_ARG;
+                goto done;
+            }
+            // the swap: the handle owns the grown buffers, the old ones (and the staging buffer of
+            // host right-hand sides, sized by the old m) go
+            const int64_t mo = m - job.r;
+            bt->bytes -= (int64_t)(sizeof(double) * nlp * dlp::state_doubles(mo, n));
+            (void)hipFree(bt->dS);
+            if (bt->dBlast) {
+                bt->bytes -= (int64_t)(sizeof(double) * nlp * mo);
+                (void)hipFree(bt->dBlast);
+            }
+            if (bt->dRb) {
+                bt->bytes -= (int64_t)(sizeof(double) * nlp * mo);
+                (void)hipFree(bt->dRb);
+                bt->dRb = nullptr;
+            }
+            bt->dS = newS;
+            bt->dBlast = newL;
+            newS = newL = nullptr;
+            bt->bytes += (int64_t)(sizeof(double) * nlp * (dlp::state_doubles(m, n) + m));
+            bt->m = m;
+            bt->reg = !force_lds && m == 64 && nw >= 1 && nw <= 3;   // the kernel of the later resolve calls
+        }
         // read back only what the caller asked for: the packed outputs it wants in one copy
         // (objective | pivot counts | status are contiguous), basis, logs, x and y when requested
         const bool wo = objective != nullptr, wn = npivots != nullptr, ws = status != nullptr;
@@ -1793,7 +2003,9 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
     }
 done:
     if (dStamps) (void)hipFree(dStamps);
-    if (rc != DLP_OK || c == &priv) c->free_all();   // a failed context is rebuilt next call
+    if (newS) (void)hipFree(newS);
+    if (newL) (void)hipFree(newL);
+    if ((rc != DLP_OK && !refused) || c == &priv) c->free_all();   // a failed context is rebuilt next call
     return rc;
 }
 }  // namespace
@@ -1923,6 +2135,34 @@ extern "C" int dlp_batch_resolve_rhs(dlp_batch* batch, const double* b, int64_t 
     job.vec = b;
     job.vstride = strideb;
     job.vec_device = b_is_device;
+    return batched_run(o, job);
+}
+
+extern "C" int dlp_batch_add_rows(dlp_batch* batch, int64_t r, const double* G, int64_t strideG, const double* h,
+                                  int64_t strideh, int rows_are_device, int64_t max_pivots, const dlp_batch_out* out) {
+    if (!batch || r < 0 || max_pivots < 0 || (out && out->log_cap < 0) ||
+        (rows_are_device != 0 && rows_are_device != 1) ||
+        (r > 0 && (!G || !h || (strideG != 0 && strideG < r * batch->n) || (strideh != 0 && strideh < r)))) {
+        dlp::set_error("dlp_batch_add_rows: bad arguments");
+        return DLP_ERR_ARG;
+    }
+    if (r > 160 * 1024 / 8) {   // (a row takes more than 8 bytes of LDS: the launch's formula cannot hold it)
+        dlp::set_error("dlp_batch_add_rows: tableau does not fit in 160 KiB of LDS");
+        return DLP_ERR_UNSUPPORTED;
+    }
+    dlp_options o = batch->opt;
+    o.max_pivots = max_pivots;
+    BatchJob job{};
+    job.who = "dlp_batch_add_rows";
+    job.nlp = batch->nlp; job.m = batch->m + r; job.n = batch->n;
+    if (out) job.out = *out;
+    job.batch = batch;
+    job.resolve = true;
+    job.grow = true;
+    job.r = r;
+    job.G = G; job.h = h;
+    job.sG = strideG; job.sh = strideh;
+    job.rows_device = rows_are_device;
     return batched_run(o, job);
 }
 

@@ -639,8 +639,10 @@ class Batch:
     """A resident batch (dlp_batch_*): the LPs of batched_solve_dense solved once and kept on
     the device, then re-optimised from each LP's current basis whenever the objectives change
     (the reference's loop over its subproblems: same constraints, new weights, every
-    iteration).  A, b, c, the output switches and **opts are batched_solve_dense's; ``result``
-    is the cold solve's BatchResult.  A handle is not thread-safe."""
+    iteration).  resolve_rhs takes new right-hand sides, add_rows new constraint rows (``m``
+    grows), both by the dual simplex.  A, b, c, the output switches and **opts are
+    batched_solve_dense's; ``result`` is the cold solve's BatchResult.  A handle is not
+    thread-safe."""
 
     def __init__(self, A, b, c, *, want_x: bool = True, want_y: bool = True, want_basis: bool = False,
                  log_cap: int = 0, **opts):
@@ -745,6 +747,68 @@ class Batch:
                 "dlp_batch_resolve_rhs")
         return result()
 
+    def add_rows(self, G, h, *, max_pivots: int | None = None, want_x: bool = True, want_y: bool = True,
+                 want_basis: bool = False, log_cap: int = 0) -> BatchResult:
+        """dlp_batch_add_rows: every LP gains the r constraints G_k x <= h_k and is re-solved warm
+        by the dual simplex from its resident basis, for up to max_pivots dual pivots each
+        (default: the max_pivots of creation).  G: (nlp, r, n), or (r, n) shared by every LP; h:
+        (nlp, r), or (r,); numpy arrays or float64 tensors on the batch's device (both of one
+        kind); any finite value, negative h included.  G=None, h=None is r = 0: nothing is added
+        and every LP's dual phase continues.  After a successful call ``self.m`` has grown by r
+        (basis and y have m + r entries per LP); ``self.result`` stays creation's.  Per LP: OK,
+        INFEASIBLE, PIVOT_LIMIT (pending: call again with G=None), ERR_ARG (rejected at
+        creation) or ERR_STATE (not dual feasible: the rows are added, no pivot is done).  A NaN
+        or inf entry in any LP's rows fails the whole call (ERR_ARG) and leaves the batch as it
+        was."""
+        if (G is None) != (h is None):
+            raise ValueError("G and h must be both given or both None")
+        budget = self.max_pivots if max_pivots is None else int(max_pivots)
+        if budget < 0:
+            raise ValueError("max_pivots must be >= 0")
+        if log_cap < 0:
+            raise ValueError("log_cap must be >= 0")
+        r, ptrs, strides, on_dev = 0, (None, None), (0, 0), 0
+        if G is not None:
+            dev = [hasattr(v, "data_ptr") for v in (G, h)]
+            if any(dev) and not all(dev):
+                raise ValueError("G and h must be both numpy arrays or both device tensors")
+            shapes = []
+            if all(dev):
+                import torch
+                for name, v in (("G", G), ("h", h)):
+                    if v.dtype != torch.float64:
+                        raise ValueError(f"{name} must be a float64 tensor, not {v.dtype}")
+                    if v.device.type != "cuda" or v.device.index != self.device:
+                        raise ValueError(f"{name} is on {v.device}, the batch lives on device {self.device}")
+                    shapes.append(tuple(v.shape))
+            else:
+                G, h = np.asarray(G), np.asarray(h)
+                for name, v in (("G", G), ("h", h)):
+                    if v.dtype.kind not in "fiu":
+                        raise ValueError(f"{name} must be real-valued (float64), not {v.dtype}")
+                    shapes.append(v.shape)
+            sG, sh = shapes
+            if len(sG) not in (2, 3) or sG[-1] != self.n or sG[-2] < 1 or (len(sG) == 3 and sG[0] != self.nlp):
+                raise ValueError(f"G must have shape ({self.nlp}, r, {self.n}) or (r, {self.n}), not {sG}")
+            r = int(sG[-2])
+            if sh not in ((self.nlp, r), (r,)):
+                raise ValueError(f"h must have shape ({self.nlp}, {r}) or ({r},), not {sh}")
+            strides = (r * self.n if len(sG) == 3 else 0, r if len(sh) == 2 else 0)
+        handle = self._handle()
+        if G is not None:
+            if on_dev := int(all(dev)):
+                G, h = G.contiguous(), h.contiguous()
+                torch.cuda.current_stream(self.device).synchronize()   # G and h are complete before the call
+                ptrs = (G.data_ptr(), h.data_ptr())
+            else:
+                G, h = (np.ascontiguousarray(v, dtype=np.float64) for v in (G, h))
+                ptrs = (G.ctypes.data, h.ctypes.data)
+        out, result = _batch_outputs(self.nlp, self.m + r, self.n, want_x, want_y, want_basis, log_cap)
+        L.check(L.lib().dlp_batch_add_rows(handle, r, ptrs[0], strides[0], ptrs[1], strides[1], on_dev, budget,
+                                           C.byref(out)), "dlp_batch_add_rows")
+        self.m += r
+        return result()
+
     def read(self, k: int):
         """dlp_batch_read: LP k's resident tableau in the full layout ((m+1) x tableau_ld(m, n),
         objective row last) and its basis."""
@@ -764,7 +828,8 @@ class Batch:
     def rhs_kernel(self) -> dict:
         """dlp_batch_rhs_kernel: the kernel resolve_rhs runs for this batch (the register kernel
         at m = 64, n <= 192 unless DLP_BATCH_LDS=1 or DLP_BATCH_RHS_LDS=1) and its residency on
-        the batch's device.  info()["register_kernel"] keeps reporting the kernel of creation."""
+        the batch's device.  info()["register_kernel"] keeps reporting the kernel of creation
+        and of resolve(); after add_rows both follow the grown shape."""
         reg, lps, thr = C.c_int32(), C.c_int32(), C.c_int32()
         L.check(L.lib().dlp_batch_rhs_kernel(self._handle(), C.byref(reg), C.byref(lps), C.byref(thr)),
                 "dlp_batch_rhs_kernel")

@@ -28,6 +28,8 @@
  *     between runs, the same subproblems)              from every LP's resident basis
  *   (no reference: the same change on the one          dlp_session_set_rhs + dlp_session_run (dual
  *     global LP, R/global_problem.cpp:257-323)          pivots from the session's resident basis)
+ *   (no reference: new constraints on the same         dlp_batch_add_rows(G, h): rows added in the
+ *     subproblems: cuts, new capacities)               current basis, then the dual simplex
  *   Instance::solution_ (private, no getter)           dlp_result_x / dlp_result_y
  *     R/instance.h:34
  *   "Dual Value" stdout  R/global_problem.cpp:320-322  dlp_result_objective
@@ -782,7 +784,8 @@ int dlp_batch_resolve(dlp_batch* batch, const double* c, int64_t stridec, int c_
  *   dlp_batch_resolve do; at every other shape, or with DLP_BATCH_LDS=1 or
  *   DLP_BATCH_RHS_LDS=1 in the environment, the LDS kernel.  Both give the same bits;
  *   dlp_batch_rhs_kernel says which one runs.
- * Not covered: changes of A, c and b in one call, general LPs.  (Single sessions:
+ * Not covered: changes of A other than new rows (dlp_batch_add_rows, below), c and b in one
+ * call, general LPs.  (Single sessions:
  * dlp_session_set_rhs applies this rule to an eager session's tableau, dlp_session_set_rhs_in_place
  * to a session on any storage path.) */
 int dlp_batch_resolve_rhs(dlp_batch* batch, const double* b, int64_t strideb, int b_is_device,
@@ -790,9 +793,67 @@ int dlp_batch_resolve_rhs(dlp_batch* batch, const double* b, int64_t strideb, in
 /* The kernel dlp_batch_resolve_rhs runs for this batch: *register_kernel 1 the register-resident
  * kernel, 0 the LDS kernel; how many LPs one CU of the batch's device holds of it at once (the
  * occupancy query on that very instantiation) and its threads per LP.  NULL outputs are skipped;
- * a NULL batch is DLP_ERR_ARG.  (dlp_batch_info's register_kernel stays the kernel of creation.) */
+ * a NULL batch is DLP_ERR_ARG.  (dlp_batch_info's register_kernel stays the kernel of creation
+ * and of dlp_batch_resolve; both follow the grown shape after dlp_batch_add_rows.) */
 int dlp_batch_rhs_kernel(const dlp_batch* batch, int32_t* register_kernel, int32_t* lps_per_cu,
                          int32_t* threads_per_lp);
+/* Add r constraint rows to every resident LP and re-solve warm by the dual simplex (DESIGN.md
+ * §25): LP k gains G_k x <= h_k, G_k r x n row-major at G + k*strideG (strideG 0 = one G for all
+ * LPs, else >= r*n), h_k r doubles at h + k*strideh (0 = shared, else >= r); rows_are_device 0
+ * host / 1 device pointers on the batch's device, complete when the call is made.  Any finite
+ * value is allowed, negative h included.  The batch's m becomes m + r; n and every existing
+ * variable index stay.  New row t is row m + t, its slack variable n + m + t, basic in that row
+ * (no column is added: the record's row stride n + 1 stays).  Then the dual simplex of
+ * dlp_batch_resolve_rhs continues from the tableau as it then stands: its leaving-row rule,
+ * entering-slot rule, update, log entry, Bland rule and stops ("no eligible row" before the
+ * budget, never a primal phase), with the tol_feas, tol_piv, tol_dj and pricing of creation.
+ * out as in dlp_batch_resolve_rhs: basis and y have m + r entries per LP, npivots and the logs
+ * are this call's.
+ *
+ * Row rule.  For LP k and new row t let g be row t of G_k and, for the old rows i < m,
+ *   gB_i = g[basis[i]] if basis[i] < n, else +0.0.  For every stored slot s (variable v = var[s])
+ *   and for the RHS:
+ *     acc = g_v for a structural v < n, +0.0 for a slack, h_t for the RHS;
+ *     for i = 0 .. m-1 ascending, rows with gB_i == 0.0 skipped: acc = acc - (gB_i * T[i][s])
+ *     (the product rounded, then the difference: no fma);  T[m+t][s] = acc.
+ *   One ascending fold per entry, over the OLD rows only (the new rows do not see each other):
+ *   no atomics, no tree, nothing that depends on the launch.  Old constraint rows and the
+ *   objective row keep their bits; the objective row becomes row m + r.  basis[m+t] = n + m + t;
+ *   var[] is unchanged.  In dlp_batch_read's layout (now (m+r+1) x dlp_tableau_ld(m+r, n)) a new
+ *   row has +0.0 in every basic column and 1.0 at its own slack, old rows +0.0 in the new slack
+ *   columns.  The Bland state is reset as dlp_batch_resolve_rhs resets it.
+ * r == 0 (G, h may be NULL) adds nothing and continues every LP's dual phase from the tableau as
+ *   it stands: a pending LP with its stored Bland state, the others with a reset one.  A budget
+ *   of 1 followed by r == 0 calls gives the pivots, basis and objective bits of one unbounded
+ *   call.  r > 0 invalidates the record of each LP's last b_k (no finite b matches it): a later
+ *   dlp_batch_resolve_rhs always rebuilds, from a b of m + r entries.
+ * Per-LP outcomes, checked in the kernel in this order:
+ *   1. rejected at creation: stays rejected in the new shape (DLP_ERR_ARG, NaN values, the slack
+ *      basis of length m + r);
+ *   2. not dual feasible, some stored z_s < -tol_dj (an LP stopped inside a primal solve, or
+ *      unbounded): the rows are still added by the rule (it holds for any basis), no pivot is
+ *      done, this call reports DLP_ERR_STATE with NaN values and the basis as it stands.  If no
+ *      new RHS entry lies below -tol_feas the stored status stays as it was, so dlp_batch_resolve
+ *      can continue or restart its primal solve on the larger LP; otherwise the record is stored
+ *      pending and both later resolve calls refuse it: such an LP is solved cold;
+ *   3. DLP_INFEASIBLE or pending from an earlier dual phase: accepted, the rows are added and
+ *      the dual phase runs again.
+ * Call-level errors leave the batch bit for bit as it was and out untouched, in this order:
+ *   DLP_ERR_ARG (NULL batch, r < 0, r > 0 with NULL G or h, a stride that is neither 0 nor
+ *   >= r*n / r, rows_are_device not 0 / 1, negative max_pivots or log_cap); DLP_ERR_UNSUPPORTED
+ *   (the grown tableau does not fit 160 KiB of LDS by the launch's formula); DLP_ERR_OOM (the new
+ *   buffers do not fit); DLP_ERR_ARG with the first offending LP named in dlp_last_error when a
+ *   G_k / h_k entry is not finite (checked in the kernel, host and device rows alike: the kernel
+ *   writes the grown records into new buffers, which the handle takes only when no LP raised
+ *   the flag, so a shape change is all or nothing).
+ * Afterwards dlp_batch_info reports m + r and the new device_bytes, and its register_kernel and
+ *   dlp_batch_rhs_kernel follow the new shape: a batch grown from m = 64 leaves the register
+ *   kernel for its later resolve calls (it pays the LDS kernel's per-pivot cost from then on), one
+ *   grown from 63 to 64 rows gains it (both kernels share the record layout).  This call itself
+ *   always runs the LDS kernel.
+ * Not covered: removing rows, adding columns, changing entries of existing rows, general LPs. */
+int dlp_batch_add_rows(dlp_batch* batch, int64_t r, const double* G, int64_t strideG, const double* h,
+                       int64_t strideh, int rows_are_device, int64_t max_pivots, const dlp_batch_out* out);
 /* LP k's resident tableau in the full layout of dlp_session_tableau ((m+1) x dlp_tableau_ld(m,n),
  * basic columns as exact unit vectors, their objective entries +0.0, padding +0.0) and its
  * basis (m entries).  Either pointer may be NULL. */
