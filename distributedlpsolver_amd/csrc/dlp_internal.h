@@ -403,6 +403,27 @@ hipError_t launch_cond_expand(const double* src, int64_t ld_s, int64_t n, double
 hipError_t launch_cond_pack(const double* src, int64_t ld_s, int64_t N, double* dst, int64_t ld_d, int64_t n,
                             int64_t rows_total, const int32_t* var_of, hipStream_t s);
 
+// dlp_addrows.hip: constraint rows added to a live single-rank session (dlp_session_add_rows,
+// DESIGN.md §26).  grow_copy: the old tableau (m constraint rows + the objective row, stride ld_s)
+// into the new one (stride ld_d): the constraint rows keep their index, the objective row goes to
+// row m + r; columns [0, ncopy) keep their place, column rhs_s goes to rhs_d, the rest is +0.0 (full
+// layout: ncopy = rhs_s = N, rhs_d = N + r; condensed: ncopy = rhs_s = rhs_d = n).  row_fold: rows
+// m .. m+r-1 of the new tableau by the row rule, read from the OLD tableau: rlist the ascending R
+// contributing old rows, coef the (r rounded up to add_rows_fold_group()) x R coefficients g[basis[i]]
+// (rows past r zero), G (r x n) and h (r) on the device; var_of: the condensed slot map, else NULL;
+// basic (full layout, else NULL): [ncopy] nonzero at basic columns (+0.0); slack0 (full layout, else
+// -1): the column of new row 0's own slack (1.0 at slack0 + t in row m + t).
+int add_rows_fold_group();   // new rows folded per read of an old row (RT)
+// (add_rows_launchable: whether the two launchers accept the geometry; asked before anything is changed)
+bool add_rows_launchable(int64_t ld_s, int64_t ld_d, int64_t m, int64_t r, int64_t ncopy, int64_t rhs_s,
+                         int64_t rhs_d, int64_t slack0);
+hipError_t launch_grow_copy(const double* src, int64_t ld_s, double* dst, int64_t ld_d, int64_t m, int64_t r,
+                            int64_t ncopy, int64_t rhs_s, int64_t rhs_d, hipStream_t s);
+hipError_t launch_row_fold(const double* src, int64_t ld_s, double* dst, int64_t ld_d, int64_t m, int64_t r,
+                           int64_t n, int64_t ncopy, int64_t rhs_s, int64_t rhs_d, int64_t slack0,
+                           const int32_t* rlist, const double* coef, int64_t R, const double* G, const double* h,
+                           const int32_t* var_of, const int32_t* basic, hipStream_t s);
+
 // dlp_batched.hip: free the cached dlp_batched_solve contexts of `device` (-1: all); bytes freed
 size_t batched_release(int device);
 

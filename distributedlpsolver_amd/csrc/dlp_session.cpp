@@ -2530,10 +2530,22 @@ struct StoreState {   // what the switch replaces
     dlp::Defer d;
     bool fuse_fits;
     int defer_rb, defer_rb_req, opt_defer;
+    // what dlp_session_add_rows replaces besides: the shape and everything sized by m
+    int64_t m, N, nprice, rows;
+    int32_t* basis;
+    double* colq;
+    int32_t* ro_rows;
+    double* ro_cb;
+    int32_t* ro_basic;
+    double* du_b;
+    dlp::Cand* du_part;
+    double* du_row;
 };
 StoreState store_save(const dlp_session* s) {
     return {s->width, s->ld, s->ld_full, s->g, s->T, s->prow_send, s->prow_recv, s->pp, s->partials,
-            s->ratio_blocks, s->ratio_blocks_max, s->d, s->fuse_fits, s->defer_rb, s->defer_rb_req, s->opt.defer};
+            s->ratio_blocks, s->ratio_blocks_max, s->d, s->fuse_fits, s->defer_rb, s->defer_rb_req, s->opt.defer,
+            s->m, s->N, s->nprice, s->rows, s->basis, s->colq, s->ro_rows, s->ro_cb, s->ro_basic,
+            s->du_b, s->du_part, s->du_row};
 }
 // Back to `o`, the buffers allocated since released.
 void store_restore(dlp_session* s, const StoreState& o) {
@@ -2548,9 +2560,29 @@ void store_restore(dlp_session* s, const StoreState& o) {
                      s->d.Cc != o.d.Cc ? s->d.Cc : nullptr,
                      s->d.P != o.d.P ? s->d.P : nullptr,
                      s->d.rhs != o.d.rhs ? s->d.rhs : nullptr,
-                     s->d.nzc != o.d.nzc ? s->d.nzc : nullptr};
+                     s->d.nzc != o.d.nzc ? s->d.nzc : nullptr,
+                     s->basis != o.basis ? s->basis : nullptr,
+                     s->colq != o.colq ? s->colq : nullptr,
+                     s->ro_rows != o.ro_rows ? s->ro_rows : nullptr,
+                     s->ro_cb != o.ro_cb ? s->ro_cb : nullptr,
+                     s->ro_basic != o.ro_basic ? s->ro_basic : nullptr,
+                     s->du_b != o.du_b ? s->du_b : nullptr,
+                     s->du_part != o.du_part ? s->du_part : nullptr,
+                     s->du_row != o.du_row ? s->du_row : nullptr};
     (void)hipStreamSynchronize(s->stream);   // (their memsets)
     for (void* p : fresh) pool_release(s, s->device, p);
+    s->m = o.m;
+    s->N = o.N;
+    s->nprice = o.nprice;
+    s->rows = o.rows;
+    s->basis = o.basis;
+    s->colq = o.colq;
+    s->ro_rows = o.ro_rows;
+    s->ro_cb = o.ro_cb;
+    s->ro_basic = o.ro_basic;
+    s->du_b = o.du_b;
+    s->du_part = o.du_part;
+    s->du_row = o.du_row;
     s->width = o.width;
     s->ld = o.ld;
     s->ld_full = o.ld_full;
@@ -3173,6 +3205,47 @@ int dlp_session_set_objective(dlp_session* s, const double* c, int64_t n, double
     return DLP_OK;
 }
 
+// Dual feasibility of the tableau as the device has it (reads only): the objective row entry of every
+// nonbasic variable is >= -tol_dj.  Leaves the basis (m entries) and, on the condensed layout, the
+// slots' variables (n entries) with the caller.  DLP_ERR_STATE names the first variable that fails.
+static int check_dual_feasible(dlp_session* s, const std::string& fn, std::vector<int32_t>& basis,
+                               std::vector<int32_t>& var_of) {
+    basis.assign(s->m, 0);
+    std::vector<double> z(s->N);
+    // the objective row is kept current in place whatever the open block holds, in the lookahead's z buffer
+    const double* zrow = (s->la ? s->Tb[s->zbuf] : s->T) + s->rows * s->ld;
+    HIP_TRY(hipMemcpyAsync(basis.data(), s->basis, sizeof(int32_t) * s->m, hipMemcpyDeviceToHost, s->stream));
+    if (s->g.cd.on) {
+        // the stored layout: every slot holds a nonbasic variable (var_of names it)
+        var_of.assign(s->n, 0);
+        HIP_TRY(hipMemcpyAsync(z.data(), zrow, sizeof(double) * s->n, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(var_of.data(), s->g.cd.var_of, sizeof(int32_t) * s->n, hipMemcpyDeviceToHost,
+                               s->stream));
+        CALL_TRY(poll(s));
+        for (int64_t sl = 0; sl < s->n; ++sl)
+            if (var_of[sl] >= 0 && z[sl] < -s->opt.tol_dj) {
+                set_error(fn + ": the tableau is not dual feasible (z[" + std::to_string(var_of[sl]) +
+                          "] = " + std::to_string(z[sl]) + " < -tol_dj: a session stopped inside a primal "
+                          "solve, or an unbounded one); run it to DLP_OK first");
+                return DLP_ERR_STATE;
+            }
+    } else {
+        HIP_TRY(hipMemcpyAsync(z.data(), zrow, sizeof(double) * s->N, hipMemcpyDeviceToHost, s->stream));
+        CALL_TRY(poll(s));   // (synchronises the stream; npivots and status as the device has them)
+        std::vector<uint8_t> basic(s->N, 0);
+        for (int64_t i = 0; i < s->m; ++i)
+            if (basis[i] >= 0 && basis[i] < s->N) basic[basis[i]] = 1;
+        for (int64_t j = 0; j < s->N; ++j)
+            if (!basic[j] && z[j] < -s->opt.tol_dj) {
+                set_error(fn + ": the tableau is not dual feasible (z[" + std::to_string(j) +
+                          "] = " + std::to_string(z[j]) + " < -tol_dj: a session stopped inside a primal "
+                          "solve, or an unbounded one); run it to DLP_OK first");
+                return DLP_ERR_STATE;
+            }
+    }
+    return DLP_OK;
+}
+
 // Warm re-solve after new right-hand sides: the resident tableau of an optimal
 // session is dual feasible for every b and its slack columns are B^-1, so a new b needs only a
 // new RHS column (the fold of dlp_dual.hip) and dual pivots from the basis as it stands
@@ -3183,7 +3256,7 @@ static int set_rhs_impl(dlp_session* s, const double* b, int64_t m, double* kern
     const std::string fn = in_place ? "dlp_session_set_rhs_in_place" : "dlp_session_set_rhs";
     const int64_t m_user = s->general ? s->prob_dims.m : s->m;
     if (m != m_user) {
-        set_error(fn + ": b has " + std::to_string(m) + " entries, the problem " +
+        set_error(fn + ": b has " + std::to_string(m) + " entries, the session " +
                   std::to_string(m_user) + " rows");
         return DLP_ERR_ARG;
     }
@@ -3220,41 +3293,8 @@ static int set_rhs_impl(dlp_session* s, const double* b, int64_t m, double* kern
         return DLP_ERR_STATE;
     }
     HIP_TRY(hipSetDevice(s->device));
-    // dual feasibility: the objective row and the basis as the device has them (reads only)
-    std::vector<int32_t> basis(s->m);
-    std::vector<double> z(s->N);
-    if (s->g.cd.on) {
-        // the stored layout: every slot holds a nonbasic variable (var_of names it); the objective row
-        // is kept current in place whatever the open block holds, in the lookahead's z buffer
-        const double* zrow = (s->la ? s->Tb[s->zbuf] : s->T) + s->rows * s->ld;
-        std::vector<int32_t> var_of(s->n);
-        HIP_TRY(hipMemcpyAsync(z.data(), zrow, sizeof(double) * s->n, hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipMemcpyAsync(var_of.data(), s->g.cd.var_of, sizeof(int32_t) * s->n, hipMemcpyDeviceToHost,
-                               s->stream));
-        CALL_TRY(poll(s));
-        for (int64_t sl = 0; sl < s->n; ++sl)
-            if (var_of[sl] >= 0 && z[sl] < -s->opt.tol_dj) {
-                set_error(fn + ": the tableau is not dual feasible (z[" + std::to_string(var_of[sl]) +
-                          "] = " + std::to_string(z[sl]) + " < -tol_dj: a session stopped inside a primal "
-                          "solve, or an unbounded one); run it to DLP_OK first");
-                return DLP_ERR_STATE;
-            }
-    } else {
-        const double* zrow = (s->la ? s->Tb[s->zbuf] : s->T) + s->rows * s->ld;
-        HIP_TRY(hipMemcpyAsync(basis.data(), s->basis, sizeof(int32_t) * s->m, hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipMemcpyAsync(z.data(), zrow, sizeof(double) * s->N, hipMemcpyDeviceToHost, s->stream));
-        CALL_TRY(poll(s));   // (synchronises the stream; npivots and status as the device has them)
-        std::vector<uint8_t> basic(s->N, 0);
-        for (int64_t i = 0; i < s->m; ++i)
-            if (basis[i] >= 0 && basis[i] < s->N) basic[basis[i]] = 1;
-        for (int64_t j = 0; j < s->N; ++j)
-            if (!basic[j] && z[j] < -s->opt.tol_dj) {
-                set_error(fn + ": the tableau is not dual feasible (z[" + std::to_string(j) +
-                          "] = " + std::to_string(z[j]) + " < -tol_dj: a session stopped inside a primal "
-                          "solve, or an unbounded one); run it to DLP_OK first");
-                return DLP_ERR_STATE;
-            }
-    }
+    std::vector<int32_t> basis, var_of;
+    CALL_TRY(check_dual_feasible(s, fn, basis, var_of));
     if (deferred) {
         // the dual blocks are single-buffer ones (the step API's rule): the lookahead drained and
         // off, a block the step API left open applied; T and the objective row both in s->T
@@ -3541,6 +3581,323 @@ int dlp_session_set_defer(dlp_session* s, int defer, int condensed, int lookahea
     s->opt.lookahead = s->la ? 1 : 0;
     pick_form(s);
     HIP_TRY(hipStreamSynchronize(s->stream));
+    return DLP_OK;
+}
+
+// Constraint rows added to a live session: the LP gains G x <= h, the stored tableau
+// grows by r rows (the full layout also by r slack columns), the new rows are expressed in the
+// current basis by dlp_batch_add_rows's row rule (dlp_addrows.hip), and the session is left in a
+// dual phase as dlp_session_set_rhs_in_place leaves it.  Everything is validated and every new
+// buffer allocated before anything is changed (the pending block applied and the lookahead drained
+// are not observable), so an error leaves the session as it was.
+int dlp_session_add_rows(dlp_session* s, int64_t r, const double* G, const double* h, int64_t n,
+                         double* kernel_ms) {
+    const std::string fn = "dlp_session_add_rows";
+    if (!s) {
+        set_error(fn + ": session is NULL");
+        return DLP_ERR_ARG;
+    }
+    if (r < 0) {
+        set_error(fn + ": r must be >= 0");
+        return DLP_ERR_ARG;
+    }
+    if (r == 0) {
+        if (kernel_ms) *kernel_ms = 0.0;
+        return DLP_OK;
+    }
+    if (!G || !h) {
+        set_error(fn + ": G or h is NULL");
+        return DLP_ERR_ARG;
+    }
+    const int64_t n_user = s->general ? s->prob_dims.n : s->n;
+    if (n != n_user) {
+        set_error(fn + ": G has " + std::to_string(n) + " columns, the session " + std::to_string(n_user) +
+                  " variables");
+        return DLP_ERR_ARG;
+    }
+    // creation's limits (dlp_problem_create_*): every column index is an int32
+    if (r > INT32_MAX || s->m + r > INT32_MAX || s->N + r + 1 > INT32_MAX) {
+        set_error(fn + ": n + m + r + 1 exceeds the int32 column range");
+        return DLP_ERR_ARG;
+    }
+    for (int64_t t = 0; t < r; ++t) {
+        for (int64_t j = 0; j < n; ++j)
+            if (!std::isfinite(G[t * n + j])) {
+                set_error(fn + ": G[" + std::to_string(t) + "][" + std::to_string(j) + "] is not finite");
+                return DLP_ERR_ARG;
+            }
+        if (!std::isfinite(h[t])) {
+            set_error(fn + ": h[" + std::to_string(t) + "] is not finite");
+            return DLP_ERR_ARG;
+        }
+    }
+    if (s->general) {
+        set_error(fn + ": general / MPS problems are not supported (their rows live in the standard "
+                  "form's rows and its Phase I)");
+        return DLP_ERR_UNSUPPORTED;
+    }
+    if (s->nranks > 1 || s->exchange) {
+        set_error(fn + ": single-GPU sessions only (the fold over the rows would cross the ranks of a "
+                  "row-block session)");
+        return DLP_ERR_UNSUPPORTED;
+    }
+    if (s->cluster) {
+        set_error(fn + ": a session on the one-launch small-LP path is not supported (its LDS plan is "
+                  "tied to the shape): create it with small_lp = -1");
+        return DLP_ERR_UNSUPPORTED;
+    }
+    if (s->status < 0) {
+        set_error(fn + ": the session has failed");
+        return DLP_ERR_STATE;
+    }
+    if (s->step_open) {
+        set_error(fn + ": a caller-driven step is in progress (finish it with dlp_session_step_update)");
+        return DLP_ERR_STATE;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<int32_t> basis, var_of;
+    CALL_TRY(check_dual_feasible(s, fn, basis, var_of));
+    // the dual blocks are single-buffer ones: the lookahead drained and off, a block the step API
+    // left open applied; T and the objective row both in s->T, every column of it current
+    if (s->la) {
+        CALL_TRY(la_disable(s));
+        drop_graph(s);
+    }
+    CALL_TRY(flush_pending(s));
+    CALL_TRY(poll(s));   // (synchronises the stream; host_st is the device's state)
+    if (s->status < 0) {
+        set_error(fn + ": the session has failed");
+        return DLP_ERR_STATE;
+    }
+
+    // ---- the fold's inputs: the contributing old rows, ascending, and each new row's coefficient on
+    // them (gB_i = g[basis[i]] of a basic structural variable; a -0.0 is zero: skipped)
+    const bool cond = s->g.cd.on != 0;
+    const int64_t m = s->m, N = s->N, m2 = m + r, N2 = N + r;
+    const int64_t RT = dlp::add_rows_fold_group();
+    const int64_t rpad = (r + RT - 1) / RT * RT;
+    std::vector<int32_t> rl;
+    for (int64_t i = 0; i < m; ++i) {
+        const int32_t v = basis[i];
+        if (v < 0 || v >= n) continue;
+        for (int64_t t = 0; t < r; ++t)
+            if (G[t * n + v] != 0.0) {
+                rl.push_back((int32_t)i);
+                break;
+            }
+    }
+    const int64_t R = (int64_t)rl.size();
+    std::vector<double> coef;
+    std::vector<int32_t> basic, tail, minus;
+    try {   // (no exception crosses the C boundary: r is the caller's, and so are these sizes)
+        coef.assign((size_t)(rpad * R), 0.0);
+        basic.assign(cond ? 0 : N, 0);
+        tail.resize(r);
+        minus.assign(cond ? r : 0, -1);
+    } catch (const std::bad_alloc&) {
+        set_error(fn + ": out of host memory for the fold's coefficients");
+        return DLP_ERR_OOM;
+    }
+    for (int64_t t = 0; t < r; ++t)
+        for (int64_t k = 0; k < R; ++k) coef[(size_t)(t * R + k)] = G[t * n + basis[rl[k]]];
+    if (!cond)
+        for (int64_t i = 0; i < m; ++i)
+            if (basis[i] >= 0 && basis[i] < N) basic[basis[i]] = 1;
+
+    // ---- the new plan and its buffers, beside the old ones
+    const StoreState old = store_save(s);
+    const int K = s->d.K;
+    const bool deferred = K > 1 || cond;
+    s->m = m2;
+    s->N = N2;
+    s->nprice = N2;
+    s->rows = m2;
+    s->g.rows = m2;
+    s->g.rows_elig = m2;
+    s->T = nullptr;
+    s->prow_send = s->prow_recv = nullptr;
+    s->pp = nullptr;
+    s->basis = nullptr;
+    s->colq = nullptr;
+    s->ro_rows = nullptr;
+    s->ro_cb = nullptr;
+    s->ro_basic = nullptr;
+    s->du_b = nullptr;
+    s->du_part = nullptr;
+    s->du_row = nullptr;
+    s->g.cd = dlp::Cond{};
+    s->d = dlp::Defer{};
+    s->d.K = K;
+    s->d.form = old.d.form;
+    set_layout(s, cond);   // creation's strides for the session's ld_align at the new width
+    plan_side(s);
+    const int64_t rows_total = m2 + 1;
+    const int64_t ncopy = cond ? s->n : N, rhs_s = ncopy, rhs_d = cond ? s->n : N2;
+    if (!dlp::add_rows_launchable(old.ld, s->ld, m, r, ncopy, rhs_s, rhs_d, cond ? -1 : N)) {
+        store_restore(s, old);   // (nothing allocated yet)
+        set_error(fn + ": the grown shape is beyond the kernels' grid limits");
+        return DLP_ERR_ARG;
+    }
+    // the call's own inputs on the device: G, h, the row list, the coefficients, the basic flags
+    double *dG = nullptr, *dh = nullptr, *dcoef = nullptr;
+    int32_t *drl = nullptr, *dbasic = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    auto alloc = [&](void** p, size_t bytes) {
+        return pool_alloc(s, s->device, p, std::max<size_t>(bytes, 8)) == hipSuccess ? DLP_OK : DLP_ERR_OOM;
+    };
+    int rc = DLP_OK;
+    if (cond) rc = alloc_cond_maps(s);
+    if (rc == DLP_OK) rc = alloc((void**)&s->T, (size_t)rows_total * s->ld * sizeof(double));
+    s->g.T = s->T;
+    if (rc == DLP_OK) rc = alloc_stride_arrays(s);
+    if (rc == DLP_OK && s->ratio_blocks_max > old.ratio_blocks_max) {
+        s->partials = nullptr;
+        rc = alloc((void**)&s->partials, sizeof(dlp::Cand) * s->ratio_blocks_max);
+    } else {
+        s->ratio_blocks_max = std::max(s->ratio_blocks_max, old.ratio_blocks_max);   // (the capacity)
+    }
+    if (rc == DLP_OK) rc = alloc((void**)&s->basis, sizeof(int32_t) * m2);
+    if (rc == DLP_OK) rc = alloc((void**)&s->colq, sizeof(double) * (rows_total + dlp::kColqPad));
+    if (rc == DLP_OK && K > 1) {
+        rc = alloc_defer_arrays(s);
+        // the caller's band rows stay (dlp_session_set_tuning), fitted to the new shape
+        s->defer_rb_req = old.defer_rb_req;
+        s->defer_rb = s->defer_rb_req > 0 ? fit_defer_rb(s, s->defer_rb_req) : auto_defer_rb(s);
+    }
+    if (rc == DLP_OK) rc = alloc((void**)&s->du_b, sizeof(double) * m2);
+    if (rc == DLP_OK)
+        rc = alloc((void**)&s->du_part,
+                   sizeof(dlp::Cand) * std::max<int64_t>(std::max(dlp::dual_row_blocks(s->g), dlp::dual_col_blocks(s->g)),
+                                                         dlp::dual_defer_parts(s->g)));
+    if (rc == DLP_OK && deferred) rc = alloc((void**)&s->du_row, sizeof(double) * s->ld);
+    if (rc == DLP_OK && old.ro_rows) {   // (ro_c is sized by n: it stays)
+        rc = alloc((void**)&s->ro_rows, sizeof(int32_t) * m2);
+        if (rc == DLP_OK) rc = alloc((void**)&s->ro_cb, sizeof(double) * m2);
+    }
+    if (rc == DLP_OK && old.ro_basic && !cond) rc = alloc((void**)&s->ro_basic, sizeof(int32_t) * s->width);
+    if (rc == DLP_OK) rc = alloc((void**)&dG, sizeof(double) * r * n);
+    if (rc == DLP_OK) rc = alloc((void**)&dh, sizeof(double) * r);
+    if (rc == DLP_OK) rc = alloc((void**)&drl, sizeof(int32_t) * R);
+    if (rc == DLP_OK) rc = alloc((void**)&dcoef, sizeof(double) * rpad * R);
+    if (rc == DLP_OK && !cond) rc = alloc((void**)&dbasic, sizeof(int32_t) * N);
+    for (hipEvent_t& e : s->du_ev)
+        if (rc == DLP_OK && !e && hipEventCreate(&e) != hipSuccess) rc = DLP_ERR_HIP;
+    if (rc == DLP_OK && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess))
+        rc = DLP_ERR_HIP;
+    void* temps[] = {dG, dh, drl, dcoef, dbasic};
+    if (rc != DLP_OK) {
+        (void)hipGetLastError();
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        store_restore(s, old);   // (synchronises the stream)
+        for (void* p : temps) pool_release(s, s->device, p);
+        set_error(fn + ": the buffers of the grown tableau do not fit beside the old ones");
+        return DLP_ERR_OOM;
+    }
+
+    // ---- the growth.  The old buffers stay intact until it has succeeded: a HIP error in it puts the
+    // old shape and buffers back (the device error itself is the caller's to handle).
+    const dlp::DevState st_before = *s->host_st;
+    auto grow = [&]() -> int {
+        HIP_TRY(hipMemsetAsync(s->colq, 0, sizeof(double) * (rows_total + dlp::kColqPad), s->stream));
+        if (s->du_row) HIP_TRY(hipMemsetAsync(s->du_row, 0, sizeof(double) * s->ld, s->stream));
+        // basis[m + t] = n + m + t; the slot maps keep every slot (n stays), the new slacks are basic, no
+        // restart is pending (every block has been applied)
+        for (int64_t t = 0; t < r; ++t) tail[t] = (int32_t)(N + t);
+        HIP_TRY(hipMemcpyAsync(s->basis, old.basis, sizeof(int32_t) * m, hipMemcpyDeviceToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->basis + m, tail.data(), sizeof(int32_t) * r, hipMemcpyHostToDevice, s->stream));
+        if (cond) {
+            HIP_TRY(hipMemcpyAsync(s->g.cd.slot_of, old.g.cd.slot_of, sizeof(int32_t) * N, hipMemcpyDeviceToDevice,
+                                   s->stream));
+            HIP_TRY(hipMemcpyAsync(s->g.cd.slot_of + N, minus.data(), sizeof(int32_t) * r, hipMemcpyHostToDevice,
+                                   s->stream));
+            HIP_TRY(hipMemcpyAsync(s->g.cd.var_of, old.g.cd.var_of, sizeof(int32_t) * s->ld, hipMemcpyDeviceToDevice,
+                                   s->stream));
+            HIP_TRY(hipMemsetAsync(s->g.cd.rst, 0xff, sizeof(int32_t) * s->ld, s->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(dG, G, sizeof(double) * r * n, hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(dh, h, sizeof(double) * r, hipMemcpyHostToDevice, s->stream));
+        if (R > 0) {
+            HIP_TRY(hipMemcpyAsync(drl, rl.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(dcoef, coef.data(), sizeof(double) * rpad * R, hipMemcpyHostToDevice, s->stream));
+        }
+        if (!cond)
+            HIP_TRY(hipMemcpyAsync(dbasic, basic.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipEventRecord(ev[0], s->stream));
+        HIP_TRY(dlp::launch_grow_copy(old.T, old.ld, s->T, s->ld, m, r, ncopy, rhs_s, rhs_d, s->stream));
+        HIP_TRY(dlp::launch_row_fold(old.T, old.ld, s->T, s->ld, m, r, s->n, ncopy, rhs_s, rhs_d, cond ? -1 : N,
+                                     drl, dcoef, R, dG, dh, cond ? s->g.cd.var_of : nullptr, dbasic, s->stream));
+        HIP_TRY(hipEventRecord(ev[1], s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));   // the old buffers and the host vectors are no longer read
+        if (kernel_ms) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            *kernel_ms = ms;
+        }
+        // the state set_rhs leaves: running, the Bland state of the options, and an empty block as
+        // creation leaves it (host_st: the device's state, read by poll)
+        dlp::DevState* hs = s->host_st;
+        hs->status = DLP_RUNNING;
+        hs->q = -1;
+        hs->bland = s->opt.pricing == DLP_PRICING_BLAND ? 1 : 0;
+        hs->blk = 0;
+        for (int l = 0; l < dlp::kMaxDefer; ++l) hs->pl[l] = -1;
+        hs->sq = -1;
+        hs->bser = 0;
+        for (auto& sl : hs->seal) {
+            sl.blk = 0;
+            sl.ser = -1;
+        }
+        HIP_TRY(hipMemcpyAsync(s->st, hs, sizeof(dlp::DevState), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        return DLP_OK;
+    };
+    rc = grow();
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    if (rc != DLP_OK) {
+        const std::string why = dlp::g_err;
+        *s->host_st = st_before;
+        store_restore(s, old);
+        for (void* p : temps) pool_release(s, s->device, p);
+        set_error(why);
+        return rc;
+    }
+
+    // ---- the old shape's buffers back to the pool
+    {
+        double* other = s->Tb[0] == old.T ? s->Tb[1] : s->Tb[0];   // a drained lookahead's second buffer
+        void* gone[] = {other, old.T, old.prow_send, old.pp, old.g.cd.slot_of, old.g.cd.var_of, old.g.cd.rst,
+                        s->partials != old.partials ? old.partials : nullptr,
+                        old.d.C, old.d.Cc, old.d.P, old.d.rhs, old.d.nzc,
+                        s->dslot[1].C != old.d.C ? s->dslot[1].C : nullptr,
+                        s->dslot[1].C != old.d.C ? s->dslot[1].Cc : nullptr,
+                        s->dslot[1].C != old.d.C ? s->dslot[1].P : nullptr,
+                        s->dslot[1].C != old.d.C ? s->dslot[1].nzc : nullptr,
+                        s->band_cnt, old.basis, old.colq, old.ro_rows, old.ro_cb, old.ro_basic, old.du_b,
+                        old.du_part, old.du_row, dG, dh, drl, dcoef, dbasic};
+        for (void* p : gone) pool_release(s, s->device, p);
+        s->Tb[0] = s->T;
+        s->Tb[1] = nullptr;
+        s->dslot[0] = s->dslot[1] = dlp::Defer{};
+        s->band_cnt = nullptr;
+        s->band_stride = 0;
+    }
+    s->tread = s->tcur = s->zbuf = s->cur = 0;
+    s->la_pending = false;
+    s->since_flush = 0;
+    s->ev_pending = 0;
+    drop_graph(s);   // windows captured on the old geometry
+    s->graph_chunk = 0;
+
+    // ---- what creation derives from the tableau: pricing partials, the RHS cache
+    HIP_TRY(dlp::launch_price_init(s->g, s->pp, s->opt.tol_dj, s->opt.update_variant, s->stream));
+    if (K > 1) HIP_TRY(dlp::launch_gather_column(s->T, s->ld, s->rows, s->g.ncols, s->d.rhs, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->prob_dims.m = m2;   // (the dlp_problem handle itself is not touched)
+    s->status = DLP_RUNNING;
+    // the pivot budget counts pivots: launches enqueued after the previous optimum did none
+    s->launched = s->npivots;
+    s->dual = true;
     return DLP_OK;
 }
 

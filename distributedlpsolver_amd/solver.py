@@ -233,10 +233,28 @@ class Session:
         L.check(L.lib().dlp_session_create_rank(problem._h, C.byref(self.opts), rank, nranks, uid,
                                                 C.byref(h)), "dlp_session_create_rank")
         self._h = h
+        self._info()
+
+    @property
+    def m(self) -> int:
+        """The live row count in the caller's terms.  A single-GPU session of a dense, random or
+        ad-allocation problem reports its own (dlp_session_info: the problem's rows plus those
+        add_rows added); a rank or a general LP has its problem's."""
+        live = getattr(self, "_live_m", None)
+        return self.problem.m if live is None else live
+
+    @property
+    def n(self) -> int:
+        return self.problem.n
+
+    def _info(self):
+        """rows, row_first, ld, ncols and storage() as the session has them now."""
         rows, first, ld, ncols = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
-        L.check(L.lib().dlp_session_info(h, C.byref(rows), C.byref(first), C.byref(ld),
+        L.check(L.lib().dlp_session_info(self._h, C.byref(rows), C.byref(first), C.byref(ld),
                                          C.byref(ncols)), "dlp_session_info")
         self.rows, self.row_first, self.ld, self.ncols = rows.value, first.value, ld.value, ncols.value
+        single = self.nranks == 1 and not self.exchange and self.problem.kind != "general"
+        self._live_m = self.rows if single else None
         self.storage()
 
     def storage(self) -> tuple[int, int, bool]:
@@ -288,8 +306,8 @@ class Session:
         c = np.asarray(c)
         if c.dtype.kind not in "fiu":
             raise ValueError(f"c must be real-valued (float64), not {c.dtype}")
-        if c.shape != (self.problem.n,):
-            raise ValueError(f"c must have shape ({self.problem.n},), not {c.shape}")
+        if c.shape != (self.n,):
+            raise ValueError(f"c must have shape ({self.n},), not {c.shape}")
         c = np.ascontiguousarray(c, dtype=np.float64)
         ms = C.c_double()
         L.check(L.lib().dlp_session_set_objective(self._h, _dptr(c), c.shape[0], C.byref(ms)),
@@ -297,7 +315,8 @@ class Session:
         return ms.value
 
     def set_rhs(self, b, in_place: bool = False) -> float:
-        """Replace the right-hand side by b (m float64 values, any sign) and put the session into
+        """Replace the right-hand side by b (m float64 values, any sign; m is the session's: the
+        problem's plus the rows add_rows added) and put the session into
         a dual phase from its current basis (dlp_session_set_rhs: a warm re-solve; run() then does
         dual pivots and ends OK or INFEASIBLE).  Eager and small-LP sessions of an optimal tableau;
         in_place=True (dlp_session_set_rhs_in_place) also accepts a deferred session, whose dual
@@ -306,8 +325,8 @@ class Session:
         b = np.asarray(b)
         if b.dtype.kind not in "fiu":
             raise ValueError(f"b must be real-valued (float64), not {b.dtype}")
-        if b.shape != (self.problem.m,):
-            raise ValueError(f"b must have shape ({self.problem.m},), not {b.shape}")
+        if b.shape != (self.m,):
+            raise ValueError(f"b must have shape ({self.m},), not {b.shape}")
         b = np.ascontiguousarray(b, dtype=np.float64)
         ms = C.c_double()
         if in_place:
@@ -316,6 +335,35 @@ class Session:
         else:
             L.check(L.lib().dlp_session_set_rhs(self._h, _dptr(b), b.shape[0], C.byref(ms)),
                     "dlp_session_set_rhs")
+        return ms.value
+
+    def add_rows(self, G, h) -> float:
+        """Add the constraint rows G x <= h to the live session and put it into a dual phase from
+        its current basis (dlp_session_add_rows; run() then does dual pivots and ends OK or
+        INFEASIBLE).  G: (r, n) or (n,) real values, h: (r,) or a scalar; any finite value.  New
+        row t is row m + t, its slack variable n + m + t.  Single-GPU sessions created with
+        small_lp=-1, eager or deferred (a lookahead is drained and turned off).  Afterwards m,
+        rows, ld, ncols and storage() describe the grown LP.  Returns the device time (ms) of the
+        two kernels of the call."""
+        G, h = np.asarray(G), np.asarray(h)
+        for name, a in (("G", G), ("h", h)):
+            if a.dtype.kind not in "fiu":
+                raise ValueError(f"{name} must be real-valued (float64), not {a.dtype}")
+        if G.ndim == 1:
+            G = G.reshape(1, -1)
+        if G.ndim != 2 or G.shape[1] != self.n:
+            raise ValueError(f"G must have shape (r, {self.n}) or ({self.n},), not {G.shape}")
+        r = G.shape[0]
+        if h.ndim == 0:
+            h = h.reshape(1)
+        if h.shape != (r,):
+            raise ValueError(f"h must have shape ({r},) for {r} rows, not {h.shape}")
+        G = np.ascontiguousarray(G, dtype=np.float64)
+        h = np.ascontiguousarray(h, dtype=np.float64)
+        ms = C.c_double()
+        L.check(L.lib().dlp_session_add_rows(self._h, r, _dptr(G), _dptr(h), self.n, C.byref(ms)),
+                "dlp_session_add_rows")
+        self._info()
         return ms.value
 
     def set_defer(self, defer: int, condensed: int = 0, lookahead: int = -1) -> float:
@@ -502,7 +550,7 @@ class Session:
     def result(self) -> Result:
         h = C.c_void_p()
         L.check(L.lib().dlp_session_result(self._h, C.byref(h)), "dlp_session_result")
-        return _result_from_handle(h, self.problem.m, self.problem.n)
+        return _result_from_handle(h, self.m, self.n)
 
     @staticmethod
     def merged_result(sessions) -> Result:

@@ -30,6 +30,8 @@
  *     global LP, R/global_problem.cpp:257-323)          pivots from the session's resident basis)
  *   (no reference: new constraints on the same         dlp_batch_add_rows(G, h): rows added in the
  *     subproblems: cuts, new capacities)               current basis, then the dual simplex
+ *   (no reference: the same on the one global LP:      dlp_session_add_rows(G, h) + dlp_session_run
+ *     a cutting-plane or lazy-constraint loop)         (the resident tableau grown, dual pivots)
  *   Instance::solution_ (private, no getter)           dlp_result_x / dlp_result_y
  *     R/instance.h:34
  *   "Dual Value" stdout  R/global_problem.cpp:320-322  dlp_result_objective
@@ -388,7 +390,8 @@ int dlp_session_set_objective(dlp_session* s, const double* c, int64_t n, double
  *
  * Errors, each leaving the session bit for bit as it was (everything is validated before anything
  * is enqueued), checked in this order:
- *   1. DLP_ERR_ARG: s or b NULL, m differs from the problem's m, a b_i that is not finite;
+ *   1. DLP_ERR_ARG: s or b NULL, m differs from the session's m (the problem's m plus the rows
+ *      dlp_session_add_rows added), a b_i that is not finite;
  *   2. DLP_ERR_UNSUPPORTED (text in dlp_last_error): a general or MPS problem; a session created
  *      with nranks > 1 or an RCCL id; a deferred session (defer > 1, full or condensed, with or
  *      without lookahead): call dlp_session_set_rhs_in_place, or create the session with defer = 1;
@@ -480,6 +483,75 @@ int dlp_session_set_rhs_in_place(dlp_session* s, const double* b, int64_t m, dou
  *   4. DLP_ERR_OOM: the new buffers do not fit; they are allocated before anything is changed.
  * Not covered: multi-rank and general-LP sessions.  (A deferred dual pivot: dlp_session_set_rhs_in_place.) */
 int dlp_session_set_defer(dlp_session* s, int defer, int condensed, int lookahead, double* kernel_ms);
+/* Add r constraint rows G x <= h to a live session and put it into a dual phase: a
+ * cut, a capacity that did not exist, a lazily generated constraint, without a new dlp_problem, a
+ * new upload and a cold solve.  G is r x n row-major, h has r entries (host pointers; any finite
+ * value, negative h included); n must be the session's n.  m becomes m + r; n and every existing
+ * variable index stay.  New row t is row m + t; its slack is variable n + m + t, basic in that row.
+ * Afterwards the session is exactly as after dlp_session_set_rhs_in_place: status DLP_RUNNING, the
+ * Bland state reset from the pricing option; dlp_session_run does dual pivots on the path the
+ * session is on and ends DLP_OK / DLP_INFEASIBLE / DLP_PIVOT_LIMIT / DLP_RUNNING ("no eligible row"
+ * comes before every budget test, so rows the optimum already satisfies give DLP_OK with 0 pivots).
+ * *kernel_ms (may be NULL): device time of the two kernels of the call together (the grow copy and
+ * the row fold, dlp_addrows.hip).  r == 0 returns DLP_OK and touches nothing (G, h may be NULL).
+ *
+ * The row rule is dlp_batch_add_rows's (below), on the session's layouts.  For new
+ * row t with g = row t of G, and the old rows i < m: gB_i = g[basis[i]] if basis[i] < n, else +0.0.
+ *   For every stored column (variable v) and for the RHS: acc = g_v (structural v < n), +0.0 (a
+ *     slack), h_t (the RHS); for i = 0 .. m-1 ascending, rows with gB_i == 0.0 skipped:
+ *     acc = acc - (gB_i * T[i][v]), the product rounded, then the difference (no fma).  One
+ *     ascending chain per entry over the old rows only (the new rows do not see each other); no
+ *     atomics, no tree over rows, nothing that depends on grid, K, layout or tuning.
+ *   Full layout, new row: every column of a currently basic variable is exact +0.0 (not folded); the
+ *     row's own slack column is 1.0; the other new slack columns and the padding are +0.0.
+ *     Elsewhere: the old rows and the objective row get +0.0 in the new slack columns; the objective
+ *     row becomes row m + r.  Old constraint rows and the objective row keep their bits, the RHS too.
+ *   Condensed layout: only the stored slots and the RHS slot exist; the slots keep their variables,
+ *     the new slacks are basic; basis[m+t] = n + m + t.
+ *   Strides: the full layout's RHS moves from column N to N + r and the stride follows creation's
+ *     rule for the session's ld_align at the new width; the condensed stride does not change.
+ *
+ * Sessions: single-GPU sessions of dense, random and ad-allocation problems on the eager path and on
+ * every deferred path (defer 2..64, full or condensed).  A session with lookahead on is accepted:
+ * it is drained and turned off, as by dlp_session_set_rhs_in_place; dlp_session_set_defer(s, K,
+ * condensed, 1) turns it on again after the phase ended DLP_OK.  A session whose earlier dual
+ * phase is pending or ended DLP_INFEASIBLE is accepted (the rule holds for any basis); a block the
+ * step API left open is applied first.  The tableau must be dual feasible (dlp_session_set_rhs's
+ * check).
+ *
+ * What follows the new shape: everything sized by m, N or a stride is rebuilt by creation's rules
+ * (the tableau, basis, slot maps, block arrays, selection plans, the pass band; captured graph
+ * windows are dropped; pricing partials and the RHS cache are regathered).  What stays: the
+ * session's size class as decided at creation (streaming or cache-resident, ld_align, the update
+ * variant, the non-temporal setting: a handful of rows does not move a tableau across those
+ * limits), K, the pass form, tolerances, pricing, the pivot log, its capacity and the life-time
+ * pivot count.  dlp_session_info, _storage, _tableau, _read_rows and _result report the grown LP (y
+ * and basis have m + r entries).  The dlp_problem handle is not touched, so the session no longer
+ * has its problem's m: dlp_session_set_rhs and _set_rhs_in_place take m + r entries,
+ * dlp_session_set_objective and _set_defer work as on any session of that shape, and so does a
+ * second dlp_session_add_rows.  The old and the new tableau coexist during the call.
+ *
+ * Errors, each leaving the session bit for bit as it was (everything is validated, and every new
+ * buffer allocated, before anything is changed), checked in this order:
+ *   1. DLP_ERR_ARG: s NULL; r < 0; r > 0 with G or h NULL; n differs from the session's n; a G or h
+ *      entry that is not finite (dlp_last_error names it); n + m + r + 1 beyond the int32 range of
+ *      creation;
+ *   2. DLP_ERR_UNSUPPORTED (text in dlp_last_error): a general or MPS problem; a session created
+ *      with nranks > 1 or an RCCL id; a session on the one-launch small-LP path (create it with
+ *      small_lp = -1: its LDS plan is tied to the shape);
+ *   3. DLP_ERR_STATE: a failed session; a caller-driven step in progress; a tableau that is not dual
+ *      feasible (dlp_session_set_rhs's test and message);
+ *   4. DLP_ERR_OOM: the grown buffers do not fit beside the old ones.  The shape, every buffer, the
+ *      status, the basis and the tableau are as before, with one difference: a lookahead that was on
+ *      has been drained and turned off (that happens before the allocation;
+ *      dlp_session_get_lookahead reports 0, dlp_session_set_defer turns it on again).
+ * A HIP error during the growth itself (DLP_ERR_HIP) puts the old shape and buffers back as well.
+ * Any r that passes check 1 is handled: the row fold takes one launch per 262,140 rows.
+ * Not covered: removing rows, adding columns, changing entries of existing rows; device-pointer G /
+ * h; small-LP, multi-rank and general-LP sessions; spare rows that would avoid the reallocation; a
+ * dual block beside a lookahead pass. */
+int dlp_session_add_rows(dlp_session* s, int64_t r, const double* G, const double* h, int64_t n,
+                         double* kernel_ms);
 int dlp_session_buffer(dlp_session* s, int which, void** dev_ptr, size_t* bytes);
 /* Synchronous host copies of an exchange buffer (for host-side communicators). */
 int dlp_session_read_buffer(dlp_session* s, int which, void* host, size_t bytes);
