@@ -60,6 +60,60 @@ def random_general(name, m, n, seed, sense=1, c0=0.0, frac_eq=0.2):
               cl, ch, c, c0=c0, sense=sense)
 
 
+def exact_general(name, m_std, nprice, seed, sense=1, dup=1, zero_e=4):
+    """Feasible and dual-feasible general LP whose standard form has exactly m_std rows and
+    nprice priced (structural + slack) columns.  Every column is [0, inf): no bound rows, so
+    m' = m.  Rows are L / G / E (E the largest share) around a sparse x0 >= 0; `dup` E rows copy
+    other E rows (redundant: their artificial stays basic), `zero_e` E rows touch only columns
+    with x0 == 0 (rhs 0: a degenerate artificial).  A flipped row (negative rhs) swaps L and G,
+    which moves the artificial count but neither m' nor nprice; the dimensions are asserted."""
+    rng = np.random.default_rng(seed)
+    m = int(m_std)
+    rkind = rng.choice(3, size=m, p=[0.25, 0.25, 0.5])   # L G E
+    eq = np.nonzero(rkind == 2)[0]
+    assert len(eq) >= 2 * dup + zero_e + 1, "too few equality rows"
+    n = int(nprice) - int((rkind != 2).sum())
+    assert n > 0
+    A = rng.standard_normal((m, n)) * (rng.random((m, n)) < 0.6)
+    x0 = rng.uniform(0.5, 2, n) * (rng.random(n) < 0.3)
+    pick = rng.permutation(eq)
+    zrows, drows, srows = pick[:zero_e], pick[zero_e:zero_e + dup], pick[zero_e + dup:zero_e + 2 * dup]
+    A[np.ix_(zrows, np.nonzero(x0)[0])] = 0.0
+    A[drows] = A[srows]
+    ax = A @ x0
+    ax[zrows] = 0.0
+    rl = np.full(m, -INF); rh = np.full(m, INF)
+    u = rng.uniform(0.1, 1, m)
+    for i, k in enumerate(rkind):
+        if k == 0: rh[i] = ax[i] + u[i]
+        elif k == 1: rl[i] = ax[i] - u[i]
+        else: rl[i] = rh[i] = ax[i]
+    # dual-feasible c (min form), as random_general: c = A^T y + d, y sign-correct, d >= 0
+    y = rng.uniform(0, 1, m)
+    y[rkind == 0] *= -1
+    y[rkind == 2] = rng.uniform(-1, 1, len(eq))
+    c = A.T @ y + rng.uniform(0, 1, n)
+    if sense == -1:
+        c = -c
+    cs = mk(name, f"build: exact-dimension general LP seed {seed} (m' {m_std}, nprice {nprice})", A, rl, rh,
+            0.0, INF, c, sense=sense)
+    dims = O.general_std_dims(fixture_lp(cs))
+    assert (dims[0], dims[2]) == (m_std, nprice), dims
+    return cs
+
+
+# The inputs of tests/test_general_defer_inputs.py (their properties, on the CPU oracle) and
+# tests/test_gpu_general_defer.py: label -> (m', nprice, seed).  Tm / Tp and Rm / Rp are the
+# sizes one below / above the 512-column pricing tile and the 128-lane ratio workgroup.
+# The seeds are the first at which the oracle alone meets every property the first file asserts.
+DEFER_INPUTS = {"S": (64, 200, 21), "T0": (128, 512, 3), "Tm": (128, 511, 1), "Tp": (128, 513, 1),
+                "Rm": (127, 390, 1), "Rp": (129, 390, 2), "W": (256, 1024, 1)}
+
+
+def defer_input(label, seed=None):
+    m, nprice, s = DEFER_INPUTS[label]
+    return exact_general(label, m, nprice, s if seed is None else seed)
+
 
 
 def fixture_lp(cs) -> "O.GeneralLP":
