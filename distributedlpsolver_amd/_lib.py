@@ -227,6 +227,8 @@ SIGNATURES = [
     ("dlp_batch_resolve_rhs", C.c_int, [_P, C.c_void_p, _I64, C.c_int, _I64, C.POINTER(BatchOut)]),
     ("dlp_batch_add_rows", C.c_int,
      [_P, _I64, C.c_void_p, _I64, C.c_void_p, _I64, C.c_int, _I64, C.POINTER(BatchOut)]),
+    ("dlp_batch_add_cols", C.c_int,
+     [_P, _I64, C.c_void_p, _I64, C.c_void_p, _I64, C.c_int, _I64, C.POINTER(BatchOut)]),
     ("dlp_batch_read", C.c_int, [_P, _I64, _DP, C.POINTER(_I32)]),
     ("dlp_batch_info", C.c_int,
      [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_I64)]),

@@ -97,12 +97,12 @@ struct BatchOut {
 // condensed tableau: slot j of row i is A_k[i][j], the RHS b_k[i], the objective row -c_k[j]
 // with value +0 (the single-LP dense fill), and no full-layout copy passes through HBM.
 struct GenIn {
-    static constexpr bool dense = false, resident = false, keep = false, dual = false, grow = false;
+    static constexpr bool dense = false, resident = false, keep = false, dual = false, grow = false, widen = false;
     const double* T;
     int64_t ld;
 };
 struct DenseIn {
-    static constexpr bool dense = true, resident = false, keep = false, dual = false, grow = false;
+    static constexpr bool dense = true, resident = false, keep = false, dual = false, grow = false, widen = false;
     const double *A, *b, *c;
     int64_t sA, sb, sc;
 };
@@ -128,7 +128,7 @@ struct DenseKeepIn : DenseIn {
     BatchState st;
 };
 struct ResIn {
-    static constexpr bool dense = false, resident = true, keep = true, dual = false, grow = false;
+    static constexpr bool dense = false, resident = true, keep = true, dual = false, grow = false, widen = false;
     BatchState st;
     const double* c;
     int64_t sc;
@@ -137,7 +137,7 @@ struct ResIn {
 // (dlp_batch_resolve_rhs): the prologue rebuilds LP k's RHS column from
 // b + k * sb by the fold of dlp.h, then the pivot loop selects the leaving row first.
 struct RhsIn {
-    static constexpr bool dense = false, resident = true, keep = true, dual = true, grow = false;
+    static constexpr bool dense = false, resident = true, keep = true, dual = true, grow = false, widen = false;
     BatchState st;
     const double* b;
     int64_t sb;
@@ -152,7 +152,7 @@ struct RhsIn {
 // the r new rows G_k x <= h_k into the current basis by the row rule of dlp.h and stores the record
 // of the grown shape at st.  r == 0: src is st.S itself, nothing is folded, `last` is not touched.
 struct AddIn {
-    static constexpr bool dense = false, resident = true, keep = true, dual = true, grow = true;
+    static constexpr bool dense = false, resident = true, keep = true, dual = true, grow = true, widen = false;
     BatchState st;
     const double* src;
     int r;
@@ -161,6 +161,24 @@ struct AddIn {
     double tol_feas;
     double* last;    // [nlp * m] of the grown shape, filled with NaN: no finite b_k continues it
     int32_t* flag;   // the smallest LP index with a G_k / h_k entry that is not finite (atomicMin)
+    static constexpr const double* c = nullptr;   // (no new objective in this call)
+    static constexpr int64_t sc = 0;
+};
+// ColsIn: the resident state widened by k structural variables per LP and continued by the primal
+// simplex (dlp_batch_add_cols).  The kernel's n is the grown column count; the
+// prologue reads LP j's record of n - k slots at src (row stride n - k + 1), re-strides it to
+// W = n + 1 with the RHS at slot n, renames every variable index >= n - k by + k, gives the new
+// variables the slots n - k .. n - 1 and fills them by the column rule of dlp.h from P_j
+// (m x k row-major at P + j * sP) and d_j (k doubles at d + j * sd); the record of the grown
+// shape is stored at st.  k > 0 always (k == 0 is dlp_batch_resolve); `last` is not touched.
+struct ColsIn {
+    static constexpr bool dense = false, resident = true, keep = true, dual = false, grow = false, widen = true;
+    BatchState st;
+    const double* src;
+    int k;
+    const double *P, *d;
+    int64_t sP, sd;
+    int32_t* flag;   // the smallest LP index with a P_j / d_j entry that is not finite (atomicMin)
     static constexpr const double* c = nullptr;   // (no new objective in this call)
     static constexpr int64_t sc = 0;
 };
@@ -246,7 +264,39 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
         }
     };
     bool has_c = false;   // (resident) a new objective: the rows are read by the fold below
-    if constexpr (In::grow) {
+    if constexpr (In::widen) {
+        // The record of n - k slots, re-strided: row i's old slots keep their place, its RHS moves
+        // to slot n, every variable index >= n - k (the slacks) goes up by k, the new variables sit
+        // nonbasic in the slots n - k .. n - 1 (filled by the column rule after the barrier).
+        // sF borrows sD as in the row growth: [0] a P_j / d_j entry that is not finite.
+        const int kc = in.k, no = n - kc, Wo = no + 1, No = no + m;
+        const double* __restrict__ src = in.src + lp * state_doubles(m, no);
+        const int32_t* __restrict__ si = (const int32_t*)(src + (m + 1) * Wo);
+        for (int s = tid; s < no; s += blockDim.x) {
+            const int v = si[s];
+            var[s] = v >= no ? v + kc : v;
+        }
+        for (int t = tid; t < kc; t += blockDim.x) var[no + t] = no + t;
+        for (int i = tid; i < m; i += blockDim.x) {
+            const int v = si[no + i];
+            basis[i] = v >= no ? v + kc : v;
+        }
+        for (int e = tid; e < (m + 1) * Wo; e += blockDim.x) {
+            const int i = e / Wo, s = e - i * Wo;
+            T[i * W + (s < no ? s : n)] = src[e];
+        }
+        if (tid == 0) {
+            // 1: rejected at creation; 3: left infeasible or pending by a dual phase (negative RHS
+            // entries: the primal rule must not pivot on it).  Both keep their stored status and
+            // Bland state in the widened record; an accepted LP starts over, whatever it was.
+            const int sv = si[No + 1];
+            const int bad = sv == DLP_ERR_ARG ? 1 : (sv == DLP_INFEASIBLE || sv == kDualPending) ? 3 : 0;
+            sI[5] = bad;
+            sI[3] = bad ? sv : (int)DLP_RUNNING;
+            sI[4] = bad ? si[No] : (pricing == DLP_PRICING_BLAND ? 1 : 0);
+            ((int32_t*)sD)[0] = 0;
+        }
+    } else if constexpr (In::grow) {
         // The record of m - r rows: its constraint rows keep their place (the stride W is the
         // grown shape's too), its objective row moves to row m, the new slacks are basic in
         // their own rows.  sF borrows sD (next written after the pivot loop's first barrier):
@@ -363,6 +413,54 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
         }
     }
     __syncthreads();
+    if constexpr (In::widen) {
+        // The column rule (dlp.h, dlp_batch_add_cols): new variable t's column in the current basis
+        // is B^-1 p, B^-1 the slack columns of the full layout, so entry r is the fold of
+        // Tfull[r][slack l] * p_l over l ascending from +0.0, the product rounded, then the sum; the
+        // objective row's entry less d_t.  inv[l] is dlp_batch_resolve_rhs's map (>= 0 slack l's
+        // slot, else -(row + 1) of the row it is basic in: that row's unit vector, every other
+        // entry a zero that changes no bit and is skipped) and borrows the entering column's
+        // place.  One work item owns one row of one new column and reads only old slots; it holds
+        // for any basis, so rejected and refused LPs take it too.
+        const int kc = in.k, no = n - kc;
+        const double* __restrict__ P = in.P + lp * in.sP;
+        const double* __restrict__ d = in.d + lp * in.sd;
+        int32_t* sF = (int32_t*)sD;
+        int32_t* inv = (int32_t*)colq;
+        bool nf = false;
+        for (int e = tid; e < m * kc; e += blockDim.x) nf |= not_finite(P[e]);
+        for (int t = tid; t < kc; t += blockDim.x) nf |= not_finite(d[t]);
+        if (__ballot(nf) != 0 && lane == 0) {
+            atomicMin(in.flag, (int32_t)lp);
+            sF[0] = 1;
+        }
+        for (int s = tid; s < no; s += blockDim.x)
+            if (var[s] >= n) inv[var[s] - n] = s;
+        for (int i = tid; i < m; i += blockDim.x)
+            if (basis[i] >= n) inv[basis[i] - n] = -(i + 1);
+        __syncthreads();
+        for (int item = tid; item < (m + 1) * kc; item += blockDim.x) {
+            const int t = item / (m + 1), r = item - t * (m + 1);
+            double acc = 0.0;
+            for (int l0 = 0; l0 < m; l0 += 8) {   // loads first, then the dependent chain
+                double cf[8], pl[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int l = min(l0 + u, m - 1);
+                    const int iv = inv[l];
+                    pl[u] = P[(int64_t)l * kc + t];
+                    cf[u] = iv >= 0 ? T[r * W + iv] : (iv == -(r + 1) ? 1.0 : 0.0);
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    if (l0 + u < m && cf[u] != 0.0) acc = fold_step(acc, cf[u], pl[u]);
+            }
+            if (r == m) acc = acc - d[t];
+            T[r * W + no + t] = acc;
+        }
+        __syncthreads();
+        if (sF[0]) return;   // (uniform) the call fails as a whole: nothing of it is kept
+    }
     if constexpr (In::grow) {
         if (in.r > 0) {
             // The row rule (dlp.h, dlp_batch_add_rows): new row t in the current basis is
@@ -445,6 +543,8 @@ __global__ __launch_bounds__(512) void batched_solve_kernel(In in, int m, int n,
             // (sI[3], sI[4]), or pending when a new row has made it primal infeasible as well
             if constexpr (In::grow)
                 if (in.r > 0) store_state(sI[5] == 3 && ((const int32_t*)sD)[1] ? kDualPending : sI[3]);
+            // (a widened one too: a shape change is all or nothing)
+            if constexpr (In::widen) store_state(sI[3]);
             return;
         }
     }
@@ -1679,6 +1779,10 @@ struct BatchJob {
     const double *G, *h;
     int64_t sG, sh;
     int rows_device;
+    // dlp_batch_add_cols: n is the grown column count, k of its columns are new; G / h / sG / sh /
+    // rows_device carry P / d / strideP / strided / cols_are_device (LP j's m x k and k doubles)
+    bool widen;
+    int64_t k;
 };
 
 int batched_run(const dlp_options& o, const BatchJob& job) {
@@ -1722,10 +1826,11 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
     }
     uint64_t* dStamps = nullptr;
     void *newS = nullptr, *newL = nullptr;   // dlp_batch_add_rows: the grown records, swapped in on success
+    void* newC = nullptr;                    // dlp_batch_add_cols: newS and the wider staging buffer of host objectives
     bool refused = false;                    // ... a non-finite row: the call fails, the context stays
     dlp::BatchOut bo{};
     const size_t bOut = (sizeof(double) + sizeof(int64_t) + sizeof(int32_t)) * (size_t)nlp;
-    const size_t bFlag = job.grow ? 16 : 0;   // (the device flag of dlp::AddIn behind the packed outputs)
+    const size_t bFlag = job.grow || job.widen ? 16 : 0;   // (the device flag of dlp::AddIn / ColsIn behind the packed outputs)
     double* dObj = nullptr;
     int64_t* dNp = nullptr;
     int32_t* dSt = nullptr;
@@ -1764,6 +1869,14 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
     }
     {
         hipStream_t s = c->s;
+        // host arrays: `per` doubles per LP at `stride` (0: one shared array) -> packed at dst
+        auto put = [&](double* dst, const double* src, int64_t per, int64_t stride) {
+            if (stride == 0 || stride == per)
+                return hipMemcpyAsync(dst, src, sizeof(double) * per * (stride ? nlp : 1),
+                                      hipMemcpyHostToDevice, s);
+            return hipMemcpy2DAsync(dst, sizeof(double) * per, src, sizeof(double) * stride,
+                                    sizeof(double) * per, (size_t)nlp, hipMemcpyHostToDevice, s);
+        };
         dlp::GenIn gin{(const double*)c->dT, ldg};
         dlp::DenseIn dn{};
         dlp::BatchState bst{bt ? (double*)bt->dS : nullptr};
@@ -1783,6 +1896,7 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
             bt->bytes += (int64_t)bL;
         }
         dlp::AddIn ain{};
+        dlp::ColsIn cin{};
         if (job.grow) {
             const int64_t r = job.r;
             ain.st = bst;
@@ -1809,19 +1923,39 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
                 } else {   // host rows: packed G | h, a shared array once
                     const size_t cntG = (size_t)(job.sG ? nlp : 1) * r * n, cnth = (size_t)(job.sh ? nlp : 1) * r;
                     HIP_BTRY(ensure_buf(&c->dIn, &c->capIn, sizeof(double) * (cntG + cnth)));
-                    auto put = [&](double* dst, const double* src, int64_t per, int64_t stride) {
-                        if (stride == 0 || stride == per)
-                            return hipMemcpyAsync(dst, src, sizeof(double) * per * (stride ? nlp : 1),
-                                                  hipMemcpyHostToDevice, s);
-                        return hipMemcpy2DAsync(dst, sizeof(double) * per, src, sizeof(double) * stride,
-                                                sizeof(double) * per, (size_t)nlp, hipMemcpyHostToDevice, s);
-                    };
                     double* dG = (double*)c->dIn;
                     HIP_BTRY(put(dG, job.G, r * n, job.sG));
                     HIP_BTRY(put(dG + cntG, job.h, r, job.sh));
                     ain.G = dG; ain.h = dG + cntG;
                     ain.sG = job.sG ? r * n : 0; ain.sh = job.sh ? r : 0;
                 }
+            }
+        } else if (job.widen) {
+            // the records of the grown shape and the staging buffer of host objectives at its n: the
+            // kernel fills the records, the handle takes both only when no LP's columns were refused
+            const int64_t k = job.k;
+            const size_t bS = sizeof(double) * nlp * dlp::state_doubles(m, n), bC = sizeof(double) * nlp * n;
+            if (hipMalloc(&newS, bS) != hipSuccess || hipMalloc(&newC, bC) != hipSuccess) {
+                (void)hipGetLastError();
+                dlp::set_error(who + ": the grown state does not fit in device memory");
+                rc = DLP_ERR_OOM;
+                goto done;
+            }
+            cin.st = dlp::BatchState{(double*)newS};
+            cin.src = (const double*)bt->dS;
+            cin.k = (int)k;
+            cin.flag = (int32_t*)((char*)c->dOut + bOut);
+            HIP_BTRY(hipMemsetAsync(cin.flag, 0x7f, sizeof(int32_t), s));   // (above every LP index)
+            if (job.rows_device) {
+                cin.P = job.G; cin.d = job.h; cin.sP = job.sG; cin.sd = job.sh;
+            } else {   // host columns: packed P | d, a shared array once
+                const size_t cntP = (size_t)(job.sG ? nlp : 1) * m * k, cntd = (size_t)(job.sh ? nlp : 1) * k;
+                HIP_BTRY(ensure_buf(&c->dIn, &c->capIn, sizeof(double) * (cntP + cntd)));
+                double* dP = (double*)c->dIn;
+                HIP_BTRY(put(dP, job.G, m * k, job.sG));
+                HIP_BTRY(put(dP + cntP, job.h, k, job.sh));
+                cin.P = dP; cin.d = dP + cntP;
+                cin.sP = job.sG ? m * k : 0; cin.sd = job.sh ? k : 0;
             }
         } else if (job.resolve) {
             if (job.vec && !job.vec_device) {   // a host vector: packed into the handle's staging buffer
@@ -1854,14 +1988,6 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
             dlp::batched_generate_kernel<<<gg, 256, 0, s>>>((double*)c->dT, ldg, m, n, job.kind, job.seed);
             HIP_BTRY(hipGetLastError());
         } else if (stage) {
-            // `per` doubles per LP at `stride` (0: one shared array) -> packed at dst
-            auto put = [&](double* dst, const double* src, int64_t per, int64_t stride) {
-                if (stride == 0 || stride == per)
-                    return hipMemcpyAsync(dst, src, sizeof(double) * per * (stride ? nlp : 1),
-                                          hipMemcpyHostToDevice, s);
-                return hipMemcpy2DAsync(dst, sizeof(double) * per, src, sizeof(double) * stride,
-                                        sizeof(double) * per, (size_t)nlp, hipMemcpyHostToDevice, s);
-            };
             double* dA = (double*)c->dIn;
             HIP_BTRY(put(dA, din->A, m * n, din->strideA));
             HIP_BTRY(put(dA + cntA, din->b, m, din->strideb));
@@ -1891,8 +2017,9 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
         const int nw = (int)((n + 63) / 64);
         // (the dual re-solve runs the register kernel's RhsIn instantiation on the same records;
         // DLP_BATCH_RHS_LDS=1 sends that call alone through the LDS kernel)
-        // (dlp_batch_add_rows always runs the LDS kernel: DESIGN.md §25)
-        const bool reg = !force_lds && m == 64 && nw >= 1 && nw <= 3 && !(job.rhs && rhs_force_lds()) && !job.grow;
+        // (dlp_batch_add_rows and dlp_batch_add_cols always run the LDS kernel: DESIGN.md §25, §27)
+        const bool reg = !force_lds && m == 64 && nw >= 1 && nw <= 3 && !(job.rhs && rhs_force_lds()) && !job.grow &&
+                         !job.widen;
         // the kernel of this input kind (its own instantiation, so its own dynamic-LDS attribute),
         // timed alone between e0 and e1
         auto launch = [&](auto in) -> hipError_t {
@@ -1904,7 +2031,7 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
             if (e == hipSuccess) e = hipEventRecord(c->e0, s);
             if (e != hipSuccess) return e;
             if (reg) {
-              if constexpr (!In::grow) {   // (no register-kernel instantiation of the growth source)
+              if constexpr (!In::grow && !In::widen) {   // (no register-kernel instantiation of the growth sources)
                 if (nw == 1)
                     dlp::batched_reg_kernel<64, 1, In><<<(unsigned)nlp, 64, 0, s>>>(in, (int)n, o.max_pivots, o.pricing,
                                                                                   o.tol_dj, o.tol_piv, bo);
@@ -1925,6 +2052,8 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
         };
         if (job.grow)
             HIP_BTRY(launch(ain));
+        else if (job.widen)
+            HIP_BTRY(launch(cin));
         else if (job.rhs)
             HIP_BTRY(launch(dlp::RhsIn{bst, dvec, dstride, o.tol_feas, (double*)bt->dBlast}));
         else if (job.resolve)
@@ -1933,7 +2062,7 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
             HIP_BTRY(launch(dlp::DenseKeepIn{dn, bst}));
         else
             HIP_BTRY(din ? launch(dn) : launch(gin));
-        if (bt && !job.rhs && !job.grow) bt->reg = reg;   // (the kernel of creation and of dlp_batch_resolve)
+        if (bt && !job.rhs && !job.grow && !job.widen) bt->reg = reg;   // (the kernel of creation and of dlp_batch_resolve)
         HIP_BTRY(hipEventRecord(c->e1, s));
         if (job.grow && job.r > 0) {
             // all or nothing: a non-finite row in any LP leaves the batch and `out` as they were
@@ -1965,6 +2094,30 @@ int batched_run(const dlp_options& o, const BatchJob& job) {
             newS = newL = nullptr;
             bt->bytes += (int64_t)(sizeof(double) * nlp * (dlp::state_doubles(m, n) + m));
             bt->m = m;
+            bt->reg = !force_lds && m == 64 && nw >= 1 && nw <= 3;   // the kernel of the later resolve calls
+        }
+        if (job.widen) {
+            // all or nothing, as above: a non-finite column in any LP leaves the batch and `out` as they were
+            int32_t* const hflag = (int32_t*)((char*)c->hOut + bOut);
+            HIP_BTRY(hipMemcpyAsync(hflag, cin.flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            HIP_BTRY(hipStreamSynchronize(s));
+            if (*hflag >= 0 && *hflag < nlp) {
+                dlp::set_error(who + ": LP " + std::to_string(*hflag) + ": a P or d entry is not finite");
+                refused = true;
+                rc = DLP_ERR_ARG;
+                goto done;
+            }
+            // the swap: the handle owns the wider records and objective staging buffer, the old ones go
+            // (`last` and the staging buffer of host right-hand sides are sized by m: they stay)
+            const int64_t no = n - job.k;
+            bt->bytes -= (int64_t)(sizeof(double) * nlp * (dlp::state_doubles(m, no) + no));
+            (void)hipFree(bt->dS);
+            (void)hipFree(bt->dC);
+            bt->dS = newS;
+            bt->dC = newC;
+            newS = newC = nullptr;
+            bt->bytes += (int64_t)(sizeof(double) * nlp * (dlp::state_doubles(m, n) + n));
+            bt->n = n;
             bt->reg = !force_lds && m == 64 && nw >= 1 && nw <= 3;   // the kernel of the later resolve calls
         }
         // read back only what the caller asked for: the packed outputs it wants in one copy
@@ -2005,6 +2158,7 @@ done:
     if (dStamps) (void)hipFree(dStamps);
     if (newS) (void)hipFree(newS);
     if (newL) (void)hipFree(newL);
+    if (newC) (void)hipFree(newC);
     if ((rc != DLP_OK && !refused) || c == &priv) c->free_all();   // a failed context is rebuilt next call
     return rc;
 }
@@ -2163,6 +2317,36 @@ extern "C" int dlp_batch_add_rows(dlp_batch* batch, int64_t r, const double* G, 
     job.G = G; job.h = h;
     job.sG = strideG; job.sh = strideh;
     job.rows_device = rows_are_device;
+    return batched_run(o, job);
+}
+
+extern "C" int dlp_batch_add_cols(dlp_batch* batch, int64_t k, const double* P, int64_t strideP, const double* d,
+                                  int64_t strided, int cols_are_device, int64_t max_pivots, const dlp_batch_out* out) {
+    if (!batch || k < 0 || max_pivots < 0 || (out && out->log_cap < 0) ||
+        (cols_are_device != 0 && cols_are_device != 1) ||
+        (k > 0 && (!P || !d || (strideP != 0 && strideP < batch->m * k) ||
+                   (strided != 0 && strided < k)))) {
+        dlp::set_error("dlp_batch_add_cols: bad arguments");
+        return DLP_ERR_ARG;
+    }
+    if (k == 0) return dlp_batch_resolve(batch, nullptr, 0, 0, max_pivots, out);
+    if (k > 160 * 1024 / 8) {   // (a column takes more than 8 bytes of LDS: the launch's formula cannot hold it)
+        dlp::set_error("dlp_batch_add_cols: tableau does not fit in 160 KiB of LDS");
+        return DLP_ERR_UNSUPPORTED;
+    }
+    dlp_options o = batch->opt;
+    o.max_pivots = max_pivots;
+    BatchJob job{};
+    job.who = "dlp_batch_add_cols";
+    job.nlp = batch->nlp; job.m = batch->m; job.n = batch->n + k;
+    if (out) job.out = *out;
+    job.batch = batch;
+    job.resolve = true;
+    job.widen = true;
+    job.k = k;
+    job.G = P; job.h = d;
+    job.sG = strideP; job.sh = strided;
+    job.rows_device = cols_are_device;
     return batched_run(o, job);
 }
 

@@ -688,7 +688,7 @@ class Batch:
     the device, then re-optimised from each LP's current basis whenever the objectives change
     (the reference's loop over its subproblems: same constraints, new weights, every
     iteration).  resolve_rhs takes new right-hand sides, add_rows new constraint rows (``m``
-    grows), both by the dual simplex.  A, b, c, the output switches and **opts are
+    grows), both by the dual simplex; add_cols takes new variables (``n`` grows), by the primal.  A, b, c, the output switches and **opts are
     batched_solve_dense's; ``result`` is the cold solve's BatchResult.  A handle is not
     thread-safe."""
 
@@ -857,6 +857,68 @@ class Batch:
         self.m += r
         return result()
 
+    def add_cols(self, P, d, *, max_pivots: int | None = None, want_x: bool = True, want_y: bool = True,
+                 want_basis: bool = False, log_cap: int = 0) -> BatchResult:
+        """dlp_batch_add_cols: every LP gains k structural variables with constraint columns P_k
+        and costs d_k (the LP becomes max [c d]^T [x; w] s.t. [A | P][x; w] <= b) and is re-solved
+        warm by the primal simplex from its resident basis, for up to max_pivots pivots each
+        (default: the max_pivots of creation).  P: (nlp, m, k), or (m, k) shared by every LP; d:
+        (nlp, k), or (k,); numpy arrays or float64 tensors on the batch's device (both of one
+        kind); any finite value.  P=None, d=None is k = 0: resolve(None).  After a successful call
+        ``self.n`` has grown by k (x has n + k entries per LP, the new variables last; slack i is
+        variable n + k + i); ``self.result`` stays creation's.  Per LP: OK, UNBOUNDED, PIVOT_LIMIT
+        (call resolve(None) to go on), ERR_ARG (rejected at creation) or ERR_STATE (infeasible or
+        pending after a dual phase: the columns are added, no pivot is done).  A NaN or inf entry
+        in any LP's columns fails the whole call (ERR_ARG) and leaves the batch as it was."""
+        if (P is None) != (d is None):
+            raise ValueError("P and d must be both given or both None")
+        budget = self.max_pivots if max_pivots is None else int(max_pivots)
+        if budget < 0:
+            raise ValueError("max_pivots must be >= 0")
+        if log_cap < 0:
+            raise ValueError("log_cap must be >= 0")
+        k, ptrs, strides, on_dev = 0, (None, None), (0, 0), 0
+        if P is not None:
+            dev = [hasattr(v, "data_ptr") for v in (P, d)]
+            if any(dev) and not all(dev):
+                raise ValueError("P and d must be both numpy arrays or both device tensors")
+            shapes = []
+            if all(dev):
+                import torch
+                for name, v in (("P", P), ("d", d)):
+                    if v.dtype != torch.float64:
+                        raise ValueError(f"{name} must be a float64 tensor, not {v.dtype}")
+                    if v.device.type != "cuda" or v.device.index != self.device:
+                        raise ValueError(f"{name} is on {v.device}, the batch lives on device {self.device}")
+                    shapes.append(tuple(v.shape))
+            else:
+                P, d = np.asarray(P), np.asarray(d)
+                for name, v in (("P", P), ("d", d)):
+                    if v.dtype.kind not in "fiu":
+                        raise ValueError(f"{name} must be real-valued (float64), not {v.dtype}")
+                    shapes.append(v.shape)
+            sP, sd = shapes
+            if len(sP) not in (2, 3) or sP[-2] != self.m or sP[-1] < 1 or (len(sP) == 3 and sP[0] != self.nlp):
+                raise ValueError(f"P must have shape ({self.nlp}, {self.m}, k) or ({self.m}, k), not {sP}")
+            k = int(sP[-1])
+            if sd not in ((self.nlp, k), (k,)):
+                raise ValueError(f"d must have shape ({self.nlp}, {k}) or ({k},), not {sd}")
+            strides = (self.m * k if len(sP) == 3 else 0, k if len(sd) == 2 else 0)
+        handle = self._handle()
+        if P is not None:
+            if on_dev := int(all(dev)):
+                P, d = P.contiguous(), d.contiguous()
+                torch.cuda.current_stream(self.device).synchronize()   # P and d are complete before the call
+                ptrs = (P.data_ptr(), d.data_ptr())
+            else:
+                P, d = (np.ascontiguousarray(v, dtype=np.float64) for v in (P, d))
+                ptrs = (P.ctypes.data, d.ctypes.data)
+        out, result = _batch_outputs(self.nlp, self.m, self.n + k, want_x, want_y, want_basis, log_cap)
+        L.check(L.lib().dlp_batch_add_cols(handle, k, ptrs[0], strides[0], ptrs[1], strides[1], on_dev, budget,
+                                           C.byref(out)), "dlp_batch_add_cols")
+        self.n += k
+        return result()
+
     def read(self, k: int):
         """dlp_batch_read: LP k's resident tableau in the full layout ((m+1) x tableau_ld(m, n),
         objective row last) and its basis."""
@@ -877,7 +939,7 @@ class Batch:
         """dlp_batch_rhs_kernel: the kernel resolve_rhs runs for this batch (the register kernel
         at m = 64, n <= 192 unless DLP_BATCH_LDS=1 or DLP_BATCH_RHS_LDS=1) and its residency on
         the batch's device.  info()["register_kernel"] keeps reporting the kernel of creation
-        and of resolve(); after add_rows both follow the grown shape."""
+        and of resolve(); after add_rows and add_cols both follow the grown shape."""
         reg, lps, thr = C.c_int32(), C.c_int32(), C.c_int32()
         L.check(L.lib().dlp_batch_rhs_kernel(self._handle(), C.byref(reg), C.byref(lps), C.byref(thr)),
                 "dlp_batch_rhs_kernel")

@@ -32,6 +32,8 @@
  *     subproblems: cuts, new capacities)               current basis, then the dual simplex
  *   (no reference: the same on the one global LP:      dlp_session_add_rows(G, h) + dlp_session_run
  *     a cutting-plane or lazy-constraint loop)         (the resident tableau grown, dual pivots)
+ *   (no reference: a new advertiser or bid in the      dlp_batch_add_cols(P, d): columns added in the
+ *     same subproblems; a priced-out column)           current basis, then the primal simplex
  *   Instance::solution_ (private, no getter)           dlp_result_x / dlp_result_y
  *     R/instance.h:34
  *   "Dual Value" stdout  R/global_problem.cpp:320-322  dlp_result_objective
@@ -547,7 +549,8 @@ int dlp_session_set_defer(dlp_session* s, int defer, int condensed, int lookahea
  *      dlp_session_get_lookahead reports 0, dlp_session_set_defer turns it on again).
  * A HIP error during the growth itself (DLP_ERR_HIP) puts the old shape and buffers back as well.
  * Any r that passes check 1 is handled: the row fold takes one launch per 262,140 rows.
- * Not covered: removing rows, adding columns, changing entries of existing rows; device-pointer G /
+ * Not covered: removing rows, adding columns (a batch has dlp_batch_add_cols; a dlp_session_add_cols
+ * is not built), changing entries of existing rows; device-pointer G /
  * h; small-LP, multi-rank and general-LP sessions; spare rows that would avoid the reallocation; a
  * dual block beside a lookahead pass. */
 int dlp_session_add_rows(dlp_session* s, int64_t r, const double* G, const double* h, int64_t n,
@@ -856,8 +859,8 @@ int dlp_batch_resolve(dlp_batch* batch, const double* c, int64_t stridec, int c_
  *   dlp_batch_resolve do; at every other shape, or with DLP_BATCH_LDS=1 or
  *   DLP_BATCH_RHS_LDS=1 in the environment, the LDS kernel.  Both give the same bits;
  *   dlp_batch_rhs_kernel says which one runs.
- * Not covered: changes of A other than new rows (dlp_batch_add_rows, below), c and b in one
- * call, general LPs.  (Single sessions:
+ * Not covered: changes of A other than new rows and new columns (dlp_batch_add_rows,
+ * dlp_batch_add_cols, below), c and b in one call, general LPs.  (Single sessions:
  * dlp_session_set_rhs applies this rule to an eager session's tableau, dlp_session_set_rhs_in_place
  * to a session on any storage path.) */
 int dlp_batch_resolve_rhs(dlp_batch* batch, const double* b, int64_t strideb, int b_is_device,
@@ -866,7 +869,8 @@ int dlp_batch_resolve_rhs(dlp_batch* batch, const double* b, int64_t strideb, in
  * kernel, 0 the LDS kernel; how many LPs one CU of the batch's device holds of it at once (the
  * occupancy query on that very instantiation) and its threads per LP.  NULL outputs are skipped;
  * a NULL batch is DLP_ERR_ARG.  (dlp_batch_info's register_kernel stays the kernel of creation
- * and of dlp_batch_resolve; both follow the grown shape after dlp_batch_add_rows.) */
+ * and of dlp_batch_resolve; both follow the grown shape after dlp_batch_add_rows and
+ * dlp_batch_add_cols.) */
 int dlp_batch_rhs_kernel(const dlp_batch* batch, int32_t* register_kernel, int32_t* lps_per_cu,
                          int32_t* threads_per_lp);
 /* Add r constraint rows to every resident LP and re-solve warm by the dual simplex (DESIGN.md
@@ -923,9 +927,68 @@ int dlp_batch_rhs_kernel(const dlp_batch* batch, int32_t* register_kernel, int32
  *   kernel for its later resolve calls (it pays the LDS kernel's per-pivot cost from then on), one
  *   grown from 63 to 64 rows gains it (both kernels share the record layout).  This call itself
  *   always runs the LDS kernel.
- * Not covered: removing rows, adding columns, changing entries of existing rows, general LPs. */
+ * Not covered: removing rows, changing entries of existing rows, general LPs.  (Adding columns:
+ * dlp_batch_add_cols, below.) */
 int dlp_batch_add_rows(dlp_batch* batch, int64_t r, const double* G, int64_t strideG, const double* h,
                        int64_t strideh, int rows_are_device, int64_t max_pivots, const dlp_batch_out* out);
+/* Add k structural variables (columns) to every resident LP and re-solve warm by the primal
+ * simplex: LP j becomes  max [c d]^T [x; w]  s.t.  [A_j | P_j][x; w] <= b_j,
+ * P_j m x k row-major at P + j*strideP (A's layout: concatenating A_j and P_j along the columns
+ * gives the stacked LP; strideP 0 = one P for all LPs, else >= m*k), d_j k doubles at
+ * d + j*strided (0 = shared, else >= k); cols_are_device 0 host / 1 device pointers on the
+ * batch's device, complete when the call is made.  Any finite value is allowed, negative entries
+ * and costs included.  m is the batch's current m (after any dlp_batch_add_rows).  The batch's n
+ * becomes n + k and the batch is from then on exactly a batch of shape m x (n + k): structural
+ * indices 0 .. n-1 keep their meaning, the new variables are n .. n+k-1, slack i is renamed from
+ * n + i to n + k + i (order-preserving: every tie rule by variable index keeps its order among
+ * the old variables).  dlp_batch_read gives (m+1) x dlp_tableau_ld(m, n+k) with the new columns
+ * at n .. n+k-1.  A new variable enters nonbasic at 0, so the resident basis stays primal
+ * feasible, and the primal loop of dlp_batch_resolve(c = NULL) continues on the widened tableau:
+ * every accepted LP starts with status DLP_RUNNING whatever it was (optimal, unbounded, pivot
+ * limit), the Bland state reset from the pricing option, the tolerances of creation.  A budget
+ * stop reports DLP_PIVOT_LIMIT and dlp_batch_resolve(NULL) continues it: a budget of 1 followed
+ * by dlp_batch_resolve(NULL) calls gives the bits of one unbounded call.  out as in
+ * dlp_batch_resolve: x has n + k entries per LP, y and basis m; npivots and the logs are this call's.
+ *
+ * Column rule.  For LP j and new variable t let p be column t of P_j.  For every stored row
+ *   r = 0 .. m (the objective row included):
+ *     acc = +0.0;  for l = 0 .. m-1 ascending: acc = acc + (Tfull[r][n+l] * p_l)
+ *     (the product rounded, then the sum: no fma), Tfull[.][n+l] slack l's stored slot when it is
+ *     nonbasic, its row's unit vector with objective entry +0.0 when it is basic (as in
+ *     dlp_batch_resolve_rhs's RHS rule; a +-0 coefficient changes no bit and may be skipped);
+ *     constraint rows: T[r][new] = acc;  objective row: z_new = acc - d_t (one more rounded
+ *     subtraction), so on the slack basis the column is p and z = -d_t up to the sign of a zero.
+ *   One ascending chain per entry: no atomics, no tree, nothing that depends on the launch; the
+ *   new columns do not see each other.  Old slots, the RHS, the objective value, the basis and
+ *   every LP's last b_k keep their bits; in var[] and basis[] every index >= the old n goes up
+ *   by k; the new variables take the new slots n .. n+k-1 of the record (row stride n + k + 1).
+ * k == 0 (P, d may be NULL) is dlp_batch_resolve(batch, NULL, 0, 0, max_pivots, out) exactly.
+ * Per-LP outcomes, checked in the kernel in this order (the record is always written in the new
+ *   shape: a shape change is all or nothing):
+ *   1. rejected at creation: stays DLP_ERR_ARG, NaN values, the slack basis with the renamed
+ *      indices;
+ *   2. stored status DLP_INFEASIBLE or a pending dual phase (the RHS has negative entries): the
+ *      columns are added by the rule (it holds for any basis), no pivot is done, this call
+ *      reports DLP_ERR_STATE with NaN values and the basis as it stands.  The stored status, the
+ *      Bland state and the last b_k stay, so dlp_batch_resolve_rhs or dlp_batch_add_rows(r = 0)
+ *      continue the dual phase on the wider LP if it is still dual feasible, and refuse it by
+ *      their own rule otherwise.
+ * Call-level errors leave the batch bit for bit as it was and out untouched, in this order:
+ *   DLP_ERR_ARG (NULL batch, k < 0, k > 0 with NULL P or d, a stride that is neither 0 nor
+ *   >= m*k / k, cols_are_device not 0 / 1, negative max_pivots or log_cap); DLP_ERR_UNSUPPORTED
+ *   (the m x (n+k) tableau does not fit 160 KiB of LDS by the launch's formula); DLP_ERR_OOM (the
+ *   new buffers do not fit); DLP_ERR_ARG with the first offending LP named in dlp_last_error when
+ *   a P_j / d_j entry is not finite (checked in the kernel, host and device columns alike, by
+ *   dlp_batch_add_rows's mechanism: new buffers, taken by the handle only when no LP raised the
+ *   flag).
+ * Afterwards dlp_batch_info reports n + k and the new device_bytes, and its register_kernel and
+ *   dlp_batch_rhs_kernel follow the new shape: a batch with m = 64 keeps the register kernel for
+ *   its later resolve calls while n + k <= 192 and leaves it beyond.  This call itself always
+ *   runs the LDS kernel.
+ * Not covered: removing columns, changing entries of existing columns, general LPs, a single
+ * session (a dlp_session_add_cols is not built). */
+int dlp_batch_add_cols(dlp_batch* batch, int64_t k, const double* P, int64_t strideP, const double* d,
+                       int64_t strided, int cols_are_device, int64_t max_pivots, const dlp_batch_out* out);
 /* LP k's resident tableau in the full layout of dlp_session_tableau ((m+1) x dlp_tableau_ld(m,n),
  * basic columns as exact unit vectors, their objective entries +0.0, padding +0.0) and its
  * basis (m entries).  Either pointer may be NULL. */
