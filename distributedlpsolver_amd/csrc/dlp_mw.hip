@@ -1317,6 +1317,10 @@ int dlp_mw_create(const dlp_problem* prob, const dlp_mw_options* opt, dlp_mw** o
         set_error("dlp_mw_create: needs an ad-allocation problem (dlp_problem_create_adalloc)");
         return DLP_ERR_ARG;
     }
+    if (prob->ad.adv.empty()) {   // bid_sparsity 0: nothing to allocate, and no grid to launch
+        set_error("dlp_mw_create: the ad-allocation problem has no bids");
+        return DLP_ERR_ARG;
+    }
     if (o.binary && (o.intervals < 1 || o.intervals > dlp::mw::kBinMaxRatios)) {
         set_error("dlp_mw: binary mode needs 1 <= intervals <= 8");
         return DLP_ERR_ARG;

@@ -1028,6 +1028,10 @@ typedef struct dlp_mw_iter {   /* per-iteration report (the reference's stdout, 
     double  min_weight, max_weight, weighted_budget;
 } dlp_mw_iter;
 void dlp_mw_options_default(dlp_mw_options* opt);
+/* Refused before the device is touched (text in dlp_last_error): DLP_ERR_ARG for a problem that
+ * is not an ad-allocation problem, one without impressions or without bids (bid_sparsity 0),
+ * binary mode with intervals outside 1..8, epsilon outside (0, 1); DLP_ERR_UNSUPPORTED for an
+ * impression with more than 1023 bids (1024 points with the origin). */
 int  dlp_mw_create(const dlp_problem* adalloc, const dlp_mw_options* opt, dlp_mw** out);
 /* Run `iterations` more MW iterations; log (may be NULL) gets one entry per iteration;
  * *kernel_ms (may be NULL) the device time of the run. */

@@ -140,6 +140,14 @@ int oracle_mw_run_mode(int A, int I, double sparsity, double scaling, double eps
                        double* infeas, int32_t* infeas_idx, double* wmin, double* wmax,
                        double* budget_w, double* x_avg_out, double* weights_out, int64_t* nnz_out,
                        int32_t* levels_out, double* interval_out);
+/* The same again; regions_out (T entries, may be NULL) gets the number of envelope regions R
+ * of each iteration (sum over impressions of hull size - 1): what the GPU path sorts, and what
+ * its one-workgroup search caches in LDS while R * 16 bytes fit. */
+int oracle_mw_run_regions(int A, int I, double sparsity, double scaling, double epsilon, int T,
+                          double tol, int binary, double scale, int intervals, double* dual,
+                          double* infeas, int32_t* infeas_idx, double* wmin, double* wmax,
+                          double* budget_w, double* x_avg_out, double* weights_out, int64_t* nnz_out,
+                          int32_t* levels_out, double* interval_out, int64_t* regions_out);
 double oracle_sum_blocked(const double* x, int64_t n);
 double oracle_dexp(double x);
 double oracle_sum_fixed(const double* x, int64_t n);

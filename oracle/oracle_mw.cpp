@@ -130,12 +130,14 @@ struct Impression {
 
 }  // namespace
 
-extern "C" int oracle_mw_run_mode(int A, int I, double sparsity, double scaling, double epsilon,
-                                  int T, double tol, int binary, double scale, int intervals,
-                                  double* dual, double* infeas, int32_t* infeas_idx, double* wmin,
-                                  double* wmax, double* budget_w, double* x_avg_out,
-                                  double* weights_out, int64_t* nnz_out, int32_t* levels_out,
-                                  double* interval_out) {
+// regions_out (may be null): the number of envelope regions R of each iteration, the sum over
+// impressions of hull size - 1 (what the GPU path sorts, caches and searches over).
+extern "C" int oracle_mw_run_regions(int A, int I, double sparsity, double scaling, double epsilon,
+                                     int T, double tol, int binary, double scale, int intervals,
+                                     double* dual, double* infeas, int32_t* infeas_idx, double* wmin,
+                                     double* wmax, double* budget_w, double* x_avg_out,
+                                     double* weights_out, int64_t* nnz_out, int32_t* levels_out,
+                                     double* interval_out, int64_t* regions_out) {
     if (binary && (intervals < 1 || intervals > 8 || !(scale > 0.0))) return -2;
     int64_t nnz = 0;
     if (oracle_gen_adalloc(A, I, sparsity, scaling, &nnz, nullptr, nullptr, nullptr, nullptr,
@@ -224,6 +226,11 @@ extern "C" int oracle_mw_run_mode(int A, int I, double sparsity, double scaling,
                     s.cut.push_back(s.cut[k]);
             }
             s.cut.push_back(DBL_MAX);
+        }
+        if (regions_out) {
+            int64_t R = 0;
+            for (int i = 0; i < I; ++i) R += sub[i].h >= 2 ? sub[i].h - 1 : 0;
+            regions_out[t - 1] = R;
         }
         std::vector<double> beta(I, 0.0);
         std::vector<int> jstar(I, -1);
@@ -424,6 +431,17 @@ extern "C" int oracle_mw_run_mode(int A, int I, double sparsity, double scaling,
     if (x_avg_out) std::memcpy(x_avg_out, xa.data(), sizeof(double) * nnz);
     if (weights_out) std::memcpy(weights_out, w.data(), sizeof(double) * A);
     return 0;
+}
+
+extern "C" int oracle_mw_run_mode(int A, int I, double sparsity, double scaling, double epsilon,
+                                  int T, double tol, int binary, double scale, int intervals,
+                                  double* dual, double* infeas, int32_t* infeas_idx, double* wmin,
+                                  double* wmax, double* budget_w, double* x_avg_out,
+                                  double* weights_out, int64_t* nnz_out, int32_t* levels_out,
+                                  double* interval_out) {
+    return oracle_mw_run_regions(A, I, sparsity, scaling, epsilon, T, tol, binary, scale, intervals,
+                                 dual, infeas, infeas_idx, wmin, wmax, budget_w, x_avg_out,
+                                 weights_out, nnz_out, levels_out, interval_out, nullptr);
 }
 
 extern "C" int oracle_mw_run(int A, int I, double sparsity, double scaling, double epsilon,

@@ -191,6 +191,43 @@ def reference_mw_binary():
         runs=out))
 
 
+def reference_mw_edges():
+    """The reference's MW loop at the envelope-edge shapes of tests/mw_shapes.py (ENVELOPE, up to
+    354x354), 30 iterations each, through the same driver: sort mode at every shape, binary mode
+    only where every impression has a bid."""
+    import mw_shapes as S
+    ref = os.path.join(ROOT, "oracle", "_ref", "dlp_ref_mw")
+    if not os.path.exists(ref):
+        subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
+    T = 30
+    out = {}
+    for s in S.ENVELOPE:
+        for mode in ("sort", "binary"):
+            if mode == "binary" and s.empties > 0:
+                continue
+            txt = subprocess.run([ref, str(s.A), str(s.I), str(s.sparsity), str(T), mode],
+                                 capture_output=True, text=True, cwd="/tmp", check=True).stdout
+            w = re.findall(r"min weight = (\S+), max weight = (\S+)", txt)
+            run = dict(
+                A=s.A, I=s.I, sparsity=s.sparsity, iterations=T, mode=mode,
+                dual_values=[float(v) for v in re.findall(r"Dual Value = (\S+)", txt)],
+                max_infeasibility=[float(v) for v in re.findall(r"max infeasiblity was (\S+)", txt)],
+                min_weight=[float(a) for a, _ in w], max_weight=[float(b) for _, b in w])
+            if mode == "binary":
+                run["critical_interval"] = [[float(a), float(b)]
+                                            for a, b in re.findall(r"CR: \((\S+), (\S+)\)", txt)]
+            assert len(run["dual_values"]) == T, (s, mode)
+            out[f"{s.A}x{s.I}x{s.sparsity:g}/{mode}"] = run
+    dump("ref_mw_edges.json", dict(
+        source="oracle/_ref/dlp_ref_mw = reference solver sources + oracle/ref_mw_main.cpp driver, "
+               "RunMultiplicativeWeights(30, 1e-18, false) and (30, 1e-18, true, 1 - 0.01 * 0.001, 3), "
+               "long double, stdout at 6 digits.  Binary mode is recorded only at shapes where every "
+               "impression has a bid: with an impression without one the reference's binary mode "
+               "ends with SIGSEGV (seen at 61x61x0.1, 2x10x0.5 and 100x5000x0.02; sort mode runs "
+               "there), so 61x61x0.1 has a sort run only",
+        runs=out))
+
+
 # ---------------------------------------------------------------- general LPs (f4)
 INF = float("inf")
 
@@ -360,6 +397,10 @@ if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "mw_binary":
     reference_mw_binary()
     sys.exit(0)
 
+if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "mw_edges":
+    reference_mw_edges()
+    sys.exit(0)
+
 if __name__ == "__main__":
     kats()
     generated()
@@ -367,3 +408,4 @@ if __name__ == "__main__":
     reference_run()
     reference_mw_sort()
     reference_mw_binary()
+    reference_mw_edges()

@@ -324,12 +324,13 @@ def mw_scale(epsilon=0.01):
 def mw_run(A, I, sparsity=0.1, scaling=0.25, epsilon=0.01, T=300, tol=1e-18, binary=False,
            scale=None, intervals=3):
     """fp64 MW spec (oracle/oracle_mw.cpp), sort or binary mode.  Returns a dict of
-    per-iteration arrays (binary mode adds search `levels` and the final `interval`)."""
+    per-iteration arrays, among them `regions`, the envelope region count R (binary mode adds
+    search `levels` and the final `interval`)."""
     L = lib()
     if not getattr(L, "_mw_bound", False):
-        L.oracle_mw_run_mode.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
-                                         C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, _D, _D,
-                                         _I32, _D, _D, _D, _D, _D, _I64, _I32, _D]
+        L.oracle_mw_run_regions.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                            C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, _D, _D,
+                                            _I32, _D, _D, _D, _D, _D, _I64, _I32, _D, _I64]
         L.oracle_sum_blocked.restype = C.c_double
         L.oracle_sum_blocked.argtypes = [_D, C.c_int64]
         L.oracle_dexp.restype = C.c_double
@@ -345,15 +346,17 @@ def mw_run(A, I, sparsity=0.1, scaling=0.25, epsilon=0.01, T=300, tol=1e-18, bin
     n = C.c_int64()
     levels = np.zeros(T, np.int32)
     interval = np.zeros((T, 2))
+    regions = np.zeros(T, np.int64)
     if scale is None:
         scale = mw_scale(epsilon)
-    rc = L.oracle_mw_run_mode(A, I, sparsity, scaling, epsilon, T, tol, 1 if binary else 0,
-                              scale, intervals, _d(out["dual"]), _d(out["infeas"]),
-                              idx.ctypes.data_as(_I32), _d(out["wmin"]), _d(out["wmax"]),
-                              _d(out["budget"]), _d(xa), _d(w), C.byref(n),
-                              levels.ctypes.data_as(_I32), _d(interval))
+    rc = L.oracle_mw_run_regions(A, I, sparsity, scaling, epsilon, T, tol, 1 if binary else 0,
+                                 scale, intervals, _d(out["dual"]), _d(out["infeas"]),
+                                 idx.ctypes.data_as(_I32), _d(out["wmin"]), _d(out["wmax"]),
+                                 _d(out["budget"]), _d(xa), _d(w), C.byref(n),
+                                 levels.ctypes.data_as(_I32), _d(interval),
+                                 regions.ctypes.data_as(_I64))
     assert rc == 0
-    out.update(infeas_idx=idx, x_avg=xa, weights=w, nnz=n.value)
+    out.update(infeas_idx=idx, x_avg=xa, weights=w, nnz=n.value, regions=regions)
     if binary:
         out.update(levels=levels, interval=interval)
     return out
