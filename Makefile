@@ -12,7 +12,7 @@ HIPFLAGS  := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Iinc
 LIBDLP    := $(PKG)/libdlp.so
 OBJS      := build/dlp_kernels.o build/dlp_batched.o build/dlp_mw.o build/dlp_session.o build/dlp_adalloc.o \
              build/dlp_instance.o build/dlp_general.o build/dlp_chain.o build/dlp_pass.o build/dlp_cluster.o build/dlp_reopt.o \
-             build/dlp_dual.o build/dlp_relayout.o build/dlp_addrows.o
+             build/dlp_dual.o build/dlp_relayout.o build/dlp_addrows.o build/dlp_addcols.o
 
 all: $(LIBDLP) oracle tools
 

@@ -158,6 +158,7 @@ SIGNATURES = [
     ("dlp_session_set_rhs_in_place", C.c_int, [_P, _DP, _I64, _DP]),
     ("dlp_session_set_defer", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP]),
     ("dlp_session_add_rows", C.c_int, [_P, _I64, _DP, _DP, _I64, _DP]),
+    ("dlp_session_add_cols", C.c_int, [_P, _I64, _DP, _DP, _I64, _DP]),
     ("dlp_session_buffer", C.c_int, [_P, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     ("dlp_session_read_buffer", C.c_int, [_P, C.c_int, C.c_void_p, C.c_size_t]),
     ("dlp_session_write_buffer", C.c_int, [_P, C.c_int, C.c_void_p, C.c_size_t]),

@@ -424,6 +424,25 @@ hipError_t launch_row_fold(const double* src, int64_t ld_s, double* dst, int64_t
                            const int32_t* rlist, const double* coef, int64_t R, const double* G, const double* h,
                            const int32_t* var_of, const int32_t* basic, hipStream_t s);
 
+// dlp_addcols.hip: variables added to a live single-rank session (dlp_session_add_cols, DESIGN.md
+// §28).  widen_copy: the old tableau (m constraint rows + the objective row, stride ld_s) into the
+// new one (stride ld_d), every row at its own index: columns [0, n) keep their place, the `tail`
+// columns [n, n + tail) go to [n + k, n + k + tail) (full layout: tail = m, the slack block;
+// condensed: tail = 0), column rhs_s = n + tail goes to rhs_d = n + k + tail, the rest is +0.0.
+// col_fold: columns n .. n+k-1 of the new tableau by the column rule, read from the OLD tableau:
+// list the R contributing slacks ascending, each as its source (a stored column >= 0, or -(row + 1)
+// for a slack basic in `row` of a condensed session), coef the (k rounded up to
+// add_cols_fold_group()) x R coefficients p[t][entry] (rows past k zero), d (k) on the device.
+int add_cols_fold_group();   // new columns folded per read of the slack block (CT)
+// (add_cols_launchable: whether the two launchers accept the geometry; asked before anything is changed)
+bool add_cols_launchable(int64_t ld_s, int64_t ld_d, int64_t m, int64_t n, int64_t k, int64_t tail,
+                         int64_t rhs_s, int64_t rhs_d);
+hipError_t launch_widen_copy(const double* src, int64_t ld_s, double* dst, int64_t ld_d, int64_t m, int64_t n,
+                             int64_t k, int64_t tail, int64_t rhs_s, int64_t rhs_d, hipStream_t s);
+hipError_t launch_col_fold(const double* src, int64_t ld_s, double* dst, int64_t ld_d, int64_t m, int64_t n,
+                           int64_t k, int64_t tail, int64_t rhs_s, int64_t rhs_d, const int32_t* list,
+                           const double* coef, int64_t R, const double* d, hipStream_t s);
+
 // dlp_batched.hip: free the cached dlp_batched_solve contexts of `device` (-1: all); bytes freed
 size_t batched_release(int device);
 

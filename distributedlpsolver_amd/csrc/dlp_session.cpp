@@ -2540,12 +2540,15 @@ struct StoreState {   // what the switch replaces
     double* du_b;
     dlp::Cand* du_part;
     double* du_row;
+    // what dlp_session_add_cols replaces besides: n and the cost buffer sized by it
+    int64_t n;
+    double* ro_c;
 };
 StoreState store_save(const dlp_session* s) {
     return {s->width, s->ld, s->ld_full, s->g, s->T, s->prow_send, s->prow_recv, s->pp, s->partials,
             s->ratio_blocks, s->ratio_blocks_max, s->d, s->fuse_fits, s->defer_rb, s->defer_rb_req, s->opt.defer,
             s->m, s->N, s->nprice, s->rows, s->basis, s->colq, s->ro_rows, s->ro_cb, s->ro_basic,
-            s->du_b, s->du_part, s->du_row};
+            s->du_b, s->du_part, s->du_row, s->n, s->ro_c};
 }
 // Back to `o`, the buffers allocated since released.
 void store_restore(dlp_session* s, const StoreState& o) {
@@ -2568,9 +2571,12 @@ void store_restore(dlp_session* s, const StoreState& o) {
                      s->ro_basic != o.ro_basic ? s->ro_basic : nullptr,
                      s->du_b != o.du_b ? s->du_b : nullptr,
                      s->du_part != o.du_part ? s->du_part : nullptr,
-                     s->du_row != o.du_row ? s->du_row : nullptr};
+                     s->du_row != o.du_row ? s->du_row : nullptr,
+                     s->ro_c != o.ro_c ? s->ro_c : nullptr};
     (void)hipStreamSynchronize(s->stream);   // (their memsets)
     for (void* p : fresh) pool_release(s, s->device, p);
+    s->n = o.n;
+    s->ro_c = o.ro_c;
     s->m = o.m;
     s->N = o.N;
     s->nprice = o.nprice;
@@ -3898,6 +3904,338 @@ int dlp_session_add_rows(dlp_session* s, int64_t r, const double* G, const doubl
     // the pivot budget counts pivots: launches enqueued after the previous optimum did none
     s->launched = s->npivots;
     s->dual = true;
+    return DLP_OK;
+}
+
+// Variables added to a live session: the LP gains the columns P with costs d, the
+// stored tableau is widened by k columns (the full layout's slack block and RHS move right, the
+// condensed layout's RHS slot moves from n to n + k), the new columns are expressed in the current
+// basis by dlp_batch_add_cols's column rule (dlp_addcols.hip), the slacks are renamed n + k + i, and
+// the session is left in a primal phase as dlp_session_set_objective leaves it.  Everything is
+// validated and every new buffer allocated before anything is changed (the pending block applied and
+// the lookahead drained are not observable), so an error leaves the session as it was.
+int dlp_session_add_cols(dlp_session* s, int64_t k, const double* P, const double* d, int64_t m,
+                         double* kernel_ms) {
+    const std::string fn = "dlp_session_add_cols";
+    if (!s) {
+        set_error(fn + ": session is NULL");
+        return DLP_ERR_ARG;
+    }
+    if (k < 0) {
+        set_error(fn + ": k must be >= 0");
+        return DLP_ERR_ARG;
+    }
+    if (k == 0) {
+        if (kernel_ms) *kernel_ms = 0.0;
+        return DLP_OK;
+    }
+    if (!P || !d) {
+        set_error(fn + ": P or d is NULL");
+        return DLP_ERR_ARG;
+    }
+    const int64_t m_user = s->general ? s->prob_dims.m : s->m;
+    if (m != m_user) {
+        set_error(fn + ": P has " + std::to_string(m) + " rows, the session " + std::to_string(m_user) + " rows");
+        return DLP_ERR_ARG;
+    }
+    // creation's limits (dlp_problem_create_*): every column index is an int32 (before P is read)
+    if (k > INT32_MAX || s->n + k > INT32_MAX || s->N + k + 1 > INT32_MAX) {
+        set_error(fn + ": n + k + m + 1 exceeds the int32 column range");
+        return DLP_ERR_ARG;
+    }
+    for (int64_t l = 0; l < m; ++l)
+        for (int64_t t = 0; t < k; ++t)
+            if (!std::isfinite(P[l * k + t])) {
+                set_error(fn + ": P[" + std::to_string(l) + "][" + std::to_string(t) + "] is not finite");
+                return DLP_ERR_ARG;
+            }
+    for (int64_t t = 0; t < k; ++t)
+        if (!std::isfinite(d[t])) {
+            set_error(fn + ": d[" + std::to_string(t) + "] is not finite");
+            return DLP_ERR_ARG;
+        }
+    if (s->general) {
+        set_error(fn + ": general / MPS problems are not supported (their columns live in the standard "
+                  "form's columns, bounds and Phase I)");
+        return DLP_ERR_UNSUPPORTED;
+    }
+    if (s->nranks > 1 || s->exchange) {
+        set_error(fn + ": single-GPU sessions only (every rank of a row-block session would have to widen "
+                  "its rows in step)");
+        return DLP_ERR_UNSUPPORTED;
+    }
+    if (s->cluster) {
+        set_error(fn + ": a session on the one-launch small-LP path is not supported (its LDS plan is "
+                  "tied to the shape): create it with small_lp = -1");
+        return DLP_ERR_UNSUPPORTED;
+    }
+    if (s->status < 0) {
+        set_error(fn + ": the session has failed");
+        return DLP_ERR_STATE;
+    }
+    if (s->step_open) {
+        set_error(fn + ": a caller-driven step is in progress (finish it with dlp_session_step_update)");
+        return DLP_ERR_STATE;
+    }
+    if (dual_pending(s)) {
+        set_error(fn + ": a dual phase is pending or ended infeasible (the right-hand side has negative "
+                  "entries, which the primal rule must not pivot on): finish it with dlp_session_run or call "
+                  "dlp_session_set_rhs");
+        return DLP_ERR_STATE;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    // the widening reads one tableau: the lookahead drained and off, a block the step API left open
+    // applied; T and the objective row both in s->T, every column of it current
+    if (s->la) {
+        CALL_TRY(la_disable(s));
+        drop_graph(s);
+    }
+    CALL_TRY(flush_pending(s));
+    const bool cond = s->g.cd.on != 0;
+    const int64_t n = s->n, N = s->N, n2 = n + k, N2 = N + k;
+    std::vector<int32_t> basis, slot_of, var_of;
+    try {   // (no exception crosses the C boundary)
+        basis.assign(m, 0);
+        slot_of.assign(cond ? N : 0, 0);
+        var_of.assign(cond ? n : 0, 0);
+    } catch (const std::bad_alloc&) {
+        set_error(fn + ": out of host memory for the basis and the slot maps");
+        return DLP_ERR_OOM;
+    }
+    HIP_TRY(hipMemcpyAsync(basis.data(), s->basis, sizeof(int32_t) * m, hipMemcpyDeviceToHost, s->stream));
+    if (cond) {
+        HIP_TRY(hipMemcpyAsync(slot_of.data(), s->g.cd.slot_of, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(var_of.data(), s->g.cd.var_of, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s->stream));
+    }
+    CALL_TRY(poll(s));   // (synchronises the stream; host_st is the device's state)
+    if (s->status < 0) {
+        set_error(fn + ": the session has failed");
+        return DLP_ERR_STATE;
+    }
+
+    // ---- the fold's inputs: the contributing slacks, ascending, each as its source (a stored column,
+    // or -(row + 1) for a slack basic in `row` of the condensed layout), and each new column's
+    // coefficient on them (a -0.0 is zero: skipped)
+    const int64_t CT = dlp::add_cols_fold_group();
+    const int64_t kpad = (k + CT - 1) / CT * CT;
+    std::vector<int32_t> list, ll, basis2, slot2, var2;
+    std::vector<double> coef;
+    try {
+        std::vector<int32_t> row_of(cond ? m : 0, -1);   // the row where slack l is basic
+        if (cond)
+            for (int64_t i = 0; i < m; ++i)
+                if (basis[i] >= n && basis[i] < N) row_of[basis[i] - n] = (int32_t)i;
+        for (int64_t l = 0; l < m; ++l) {
+            bool any = false;
+            for (int64_t t = 0; t < k && !any; ++t) any = P[l * k + t] != 0.0;
+            if (!any) continue;
+            int32_t src = (int32_t)(n + l);
+            if (cond) src = slot_of[n + l] >= 0 ? slot_of[n + l] : -(row_of[l] + 1);
+            if (cond && slot_of[n + l] < 0 && row_of[l] < 0) {
+                set_error(fn + ": slack " + std::to_string(n + l) + " is neither basic nor in a slot");
+                return DLP_ERR_STATE;
+            }
+            list.push_back(src);
+            ll.push_back((int32_t)l);
+        }
+        const int64_t R = (int64_t)list.size();
+        coef.assign((size_t)(kpad * R), 0.0);
+        for (int64_t t = 0; t < k; ++t)
+            for (int64_t e = 0; e < R; ++e) coef[(size_t)(t * R + e)] = P[(int64_t)ll[e] * k + t];
+        // the renaming: every index >= n is raised by k; the new variables nonbasic in slots n .. n+k-1
+        basis2.resize(m);
+        for (int64_t i = 0; i < m; ++i) basis2[i] = basis[i] >= n ? (int32_t)(basis[i] + k) : basis[i];
+        if (cond) {
+            slot2.resize(N2);
+            for (int64_t v = 0; v < n; ++v) slot2[v] = slot_of[v];
+            for (int64_t t = 0; t < k; ++t) slot2[n + t] = (int32_t)(n + t);
+            for (int64_t v = n; v < N; ++v) slot2[v + k] = slot_of[v];
+        }
+    } catch (const std::bad_alloc&) {
+        set_error(fn + ": out of host memory for the fold's coefficients");
+        return DLP_ERR_OOM;
+    }
+    const int64_t R = (int64_t)list.size();
+
+    // ---- the new plan and its buffers, beside the old ones
+    const StoreState old = store_save(s);
+    const int K = s->d.K;
+    const bool deferred = K > 1 || cond;
+    s->n = n2;
+    s->N = N2;
+    s->nprice = N2;
+    s->T = nullptr;
+    s->prow_send = s->prow_recv = nullptr;
+    s->pp = nullptr;
+    s->basis = nullptr;
+    s->ro_c = nullptr;
+    s->ro_basic = nullptr;
+    s->du_part = nullptr;
+    s->du_row = nullptr;
+    s->g.cd = dlp::Cond{};
+    s->d = dlp::Defer{};
+    s->d.K = K;
+    s->d.form = old.d.form;
+    set_layout(s, cond);   // creation's strides for the session's ld_align at the new width
+    plan_side(s);
+    const int64_t rows_total = m + 1;
+    const int64_t tail = cond ? 0 : m, rhs_s = n + tail, rhs_d = n2 + tail;
+    if (!dlp::add_cols_launchable(old.ld, s->ld, m, n, k, tail, rhs_s, rhs_d)) {
+        store_restore(s, old);   // (nothing allocated yet)
+        set_error(fn + ": the widened shape is beyond the kernels' grid limits");
+        return DLP_ERR_ARG;
+    }
+    try {
+        if (cond) {
+            var2.assign(s->ld, -1);
+            for (int64_t sl = 0; sl < n; ++sl) var2[sl] = var_of[sl] >= n ? (int32_t)(var_of[sl] + k) : var_of[sl];
+            for (int64_t t = 0; t < k; ++t) var2[n + t] = (int32_t)(n + t);
+        }
+    } catch (const std::bad_alloc&) {
+        store_restore(s, old);
+        set_error(fn + ": out of host memory for the slot maps");
+        return DLP_ERR_OOM;
+    }
+    // the call's own inputs on the device: d, the source list, the coefficients
+    double *dd = nullptr, *dcoef = nullptr;
+    int32_t* dlist = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    auto alloc = [&](void** p, size_t bytes) {
+        return pool_alloc(s, s->device, p, std::max<size_t>(bytes, 8)) == hipSuccess ? DLP_OK : DLP_ERR_OOM;
+    };
+    int rc = DLP_OK;
+    if (cond) rc = alloc_cond_maps(s);
+    if (rc == DLP_OK) rc = alloc((void**)&s->T, (size_t)rows_total * s->ld * sizeof(double));
+    s->g.T = s->T;
+    if (rc == DLP_OK) rc = alloc_stride_arrays(s);
+    if (rc == DLP_OK && s->ratio_blocks_max > old.ratio_blocks_max) {
+        s->partials = nullptr;
+        rc = alloc((void**)&s->partials, sizeof(dlp::Cand) * s->ratio_blocks_max);
+    } else {
+        s->ratio_blocks_max = std::max(s->ratio_blocks_max, old.ratio_blocks_max);   // (the capacity)
+    }
+    if (rc == DLP_OK) rc = alloc((void**)&s->basis, sizeof(int32_t) * m);
+    if (rc == DLP_OK && K > 1) {
+        rc = alloc_defer_arrays(s);
+        // the caller's band rows stay (dlp_session_set_tuning), fitted to the new shape
+        s->defer_rb_req = old.defer_rb_req;
+        s->defer_rb = s->defer_rb_req > 0 ? fit_defer_rb(s, s->defer_rb_req) : auto_defer_rb(s);
+    }
+    // what set_objective / set_rhs allocated at their first call and the new shape outgrows
+    if (rc == DLP_OK && old.ro_c) rc = alloc((void**)&s->ro_c, sizeof(double) * n2);
+    if (rc == DLP_OK && old.ro_basic && !cond) rc = alloc((void**)&s->ro_basic, sizeof(int32_t) * s->width);
+    if (rc == DLP_OK && old.du_part)
+        rc = alloc((void**)&s->du_part,
+                   sizeof(dlp::Cand) * std::max<int64_t>(std::max(dlp::dual_row_blocks(s->g), dlp::dual_col_blocks(s->g)),
+                                                         dlp::dual_defer_parts(s->g)));
+    if (rc == DLP_OK && old.du_row && deferred) rc = alloc((void**)&s->du_row, sizeof(double) * s->ld);
+    if (rc == DLP_OK) rc = alloc((void**)&dd, sizeof(double) * k);
+    if (rc == DLP_OK) rc = alloc((void**)&dlist, sizeof(int32_t) * R);
+    if (rc == DLP_OK) rc = alloc((void**)&dcoef, sizeof(double) * kpad * R);
+    if (rc == DLP_OK && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess))
+        rc = DLP_ERR_HIP;
+    void* temps[] = {dd, dlist, dcoef};
+    if (rc != DLP_OK) {
+        (void)hipGetLastError();
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        store_restore(s, old);   // (synchronises the stream)
+        for (void* p : temps) pool_release(s, s->device, p);
+        set_error(fn + ": the buffers of the widened tableau do not fit beside the old ones");
+        return DLP_ERR_OOM;
+    }
+
+    // ---- the widening.  The old buffers stay intact until it has succeeded: a HIP error in it puts the
+    // old shape and buffers back (the device error itself is the caller's to handle).
+    const dlp::DevState st_before = *s->host_st;
+    auto widen = [&]() -> int {
+        if (s->du_row) HIP_TRY(hipMemsetAsync(s->du_row, 0, sizeof(double) * s->ld, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->basis, basis2.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice, s->stream));
+        if (cond) {
+            // no restart is pending (every block has been applied)
+            HIP_TRY(hipMemcpyAsync(s->g.cd.slot_of, slot2.data(), sizeof(int32_t) * N2, hipMemcpyHostToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(s->g.cd.var_of, var2.data(), sizeof(int32_t) * s->ld, hipMemcpyHostToDevice, s->stream));
+            HIP_TRY(hipMemsetAsync(s->g.cd.rst, 0xff, sizeof(int32_t) * s->ld, s->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(dd, d, sizeof(double) * k, hipMemcpyHostToDevice, s->stream));
+        if (R > 0) {
+            HIP_TRY(hipMemcpyAsync(dlist, list.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(dcoef, coef.data(), sizeof(double) * kpad * R, hipMemcpyHostToDevice, s->stream));
+        }
+        HIP_TRY(hipEventRecord(ev[0], s->stream));
+        HIP_TRY(dlp::launch_widen_copy(old.T, old.ld, s->T, s->ld, m, n, k, tail, rhs_s, rhs_d, s->stream));
+        HIP_TRY(dlp::launch_col_fold(old.T, old.ld, s->T, s->ld, m, n, k, tail, rhs_s, rhs_d, dlist, dcoef, R, dd,
+                                     s->stream));
+        HIP_TRY(hipEventRecord(ev[1], s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));   // the old buffers and the host vectors are no longer read
+        if (kernel_ms) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            *kernel_ms = ms;
+        }
+        // the state set_objective leaves: running, the Bland state of the options, and an empty block
+        // as creation leaves it (host_st: the device's state, read by poll)
+        dlp::DevState* hs = s->host_st;
+        hs->status = DLP_RUNNING;
+        hs->q = -1;
+        hs->bland = s->opt.pricing == DLP_PRICING_BLAND ? 1 : 0;
+        hs->blk = 0;
+        for (int l = 0; l < dlp::kMaxDefer; ++l) hs->pl[l] = -1;
+        hs->sq = -1;
+        hs->bser = 0;
+        for (auto& sl : hs->seal) {
+            sl.blk = 0;
+            sl.ser = -1;
+        }
+        HIP_TRY(hipMemcpyAsync(s->st, hs, sizeof(dlp::DevState), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        return DLP_OK;
+    };
+    rc = widen();
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    if (rc != DLP_OK) {
+        const std::string why = dlp::g_err;
+        *s->host_st = st_before;
+        store_restore(s, old);
+        for (void* p : temps) pool_release(s, s->device, p);
+        set_error(why);
+        return rc;
+    }
+
+    // ---- the old shape's buffers back to the pool
+    {
+        double* other = s->Tb[0] == old.T ? s->Tb[1] : s->Tb[0];   // a drained lookahead's second buffer
+        void* gone[] = {other, old.T, old.prow_send, old.pp, old.g.cd.slot_of, old.g.cd.var_of, old.g.cd.rst,
+                        s->partials != old.partials ? old.partials : nullptr,
+                        old.d.C, old.d.Cc, old.d.P, old.d.rhs, old.d.nzc,
+                        s->dslot[1].C != old.d.C ? s->dslot[1].C : nullptr,
+                        s->dslot[1].C != old.d.C ? s->dslot[1].Cc : nullptr,
+                        s->dslot[1].C != old.d.C ? s->dslot[1].P : nullptr,
+                        s->dslot[1].C != old.d.C ? s->dslot[1].nzc : nullptr,
+                        s->band_cnt, old.basis, old.ro_c, old.ro_basic, old.du_part, old.du_row, dd, dlist, dcoef};
+        for (void* p : gone) pool_release(s, s->device, p);
+        s->Tb[0] = s->T;
+        s->Tb[1] = nullptr;
+        s->dslot[0] = s->dslot[1] = dlp::Defer{};
+        s->band_cnt = nullptr;
+        s->band_stride = 0;
+    }
+    s->tread = s->tcur = s->zbuf = s->cur = 0;
+    s->la_pending = false;
+    s->since_flush = 0;
+    s->ev_pending = 0;
+    drop_graph(s);   // windows captured on the old geometry
+    s->graph_chunk = 0;
+
+    // ---- what creation derives from the tableau: pricing partials, the RHS cache
+    HIP_TRY(dlp::launch_price_init(s->g, s->pp, s->opt.tol_dj, s->opt.update_variant, s->stream));
+    if (K > 1) HIP_TRY(dlp::launch_gather_column(s->T, s->ld, s->rows, s->g.ncols, s->d.rhs, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->prob_dims.n = n2;   // (the dlp_problem handle itself is not touched)
+    s->status = DLP_RUNNING;
+    // the pivot budget counts pivots: launches enqueued after the previous optimum did none
+    s->launched = s->npivots;
+    s->dual = false;   // a primal phase
     return DLP_OK;
 }
 

@@ -245,7 +245,10 @@ class Session:
 
     @property
     def n(self) -> int:
-        return self.problem.n
+        """The live column count in the caller's terms, by the same rule as ``m`` (dlp_session_info's
+        ncols less its rows: the problem's variables plus those add_cols added)."""
+        live = getattr(self, "_live_n", None)
+        return self.problem.n if live is None else live
 
     def _info(self):
         """rows, row_first, ld, ncols and storage() as the session has them now."""
@@ -255,6 +258,7 @@ class Session:
         self.rows, self.row_first, self.ld, self.ncols = rows.value, first.value, ld.value, ncols.value
         single = self.nranks == 1 and not self.exchange and self.problem.kind != "general"
         self._live_m = self.rows if single else None
+        self._live_n = self.ncols - self.rows if single else None
         self.storage()
 
     def storage(self) -> tuple[int, int, bool]:
@@ -363,6 +367,36 @@ class Session:
         ms = C.c_double()
         L.check(L.lib().dlp_session_add_rows(self._h, r, _dptr(G), _dptr(h), self.n, C.byref(ms)),
                 "dlp_session_add_rows")
+        self._info()
+        return ms.value
+
+    def add_cols(self, P, d) -> float:
+        """Add k variables with the constraint columns P and the costs d to the live session and
+        put it into a primal phase from its current basis (dlp_session_add_cols; run() then does
+        primal pivots and ends OK or UNBOUNDED).  P: (m, k) or (m,) real values, d: (k,) or a
+        scalar; any finite value.  The new variables are n .. n+k-1; slack i is renamed from n + i
+        to n + k + i.  Single-GPU sessions created with small_lp=-1, eager or deferred (a lookahead
+        is drained and turned off).  Afterwards n, ld, ncols and storage() describe the widened LP
+        and result().x has n + k entries.  Returns the device time (ms) of the two kernels of the
+        call."""
+        P, d = np.asarray(P), np.asarray(d)
+        for name, a in (("P", P), ("d", d)):
+            if a.dtype.kind not in "fiu":
+                raise ValueError(f"{name} must be real-valued (float64), not {a.dtype}")
+        if P.ndim == 1:
+            P = P.reshape(-1, 1)
+        if P.ndim != 2 or P.shape[0] != self.m:
+            raise ValueError(f"P must have shape ({self.m}, k) or ({self.m},), not {P.shape}")
+        k = P.shape[1]
+        if d.ndim == 0:
+            d = d.reshape(1)
+        if d.shape != (k,):
+            raise ValueError(f"d must have shape ({k},) for {k} columns, not {d.shape}")
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        d = np.ascontiguousarray(d, dtype=np.float64)
+        ms = C.c_double()
+        L.check(L.lib().dlp_session_add_cols(self._h, k, _dptr(P), _dptr(d), self.m, C.byref(ms)),
+                "dlp_session_add_cols")
         self._info()
         return ms.value
 

@@ -34,6 +34,8 @@
  *     a cutting-plane or lazy-constraint loop)         (the resident tableau grown, dual pivots)
  *   (no reference: a new advertiser or bid in the      dlp_batch_add_cols(P, d): columns added in the
  *     same subproblems; a priced-out column)           current basis, then the primal simplex
+ *   (no reference: the same on the one global LP:      dlp_session_add_cols(P, d) + dlp_session_run
+ *     column generation, advertisers / bids arriving)  (the resident tableau widened, primal pivots)
  *   Instance::solution_ (private, no getter)           dlp_result_x / dlp_result_y
  *     R/instance.h:34
  *   "Dual Value" stdout  R/global_problem.cpp:320-322  dlp_result_objective
@@ -549,11 +551,92 @@ int dlp_session_set_defer(dlp_session* s, int defer, int condensed, int lookahea
  *      dlp_session_get_lookahead reports 0, dlp_session_set_defer turns it on again).
  * A HIP error during the growth itself (DLP_ERR_HIP) puts the old shape and buffers back as well.
  * Any r that passes check 1 is handled: the row fold takes one launch per 262,140 rows.
- * Not covered: removing rows, adding columns (a batch has dlp_batch_add_cols; a dlp_session_add_cols
- * is not built), changing entries of existing rows; device-pointer G /
+ * Not covered: removing rows, changing entries of existing rows (columns: dlp_session_add_cols,
+ * below); device-pointer G /
  * h; small-LP, multi-rank and general-LP sessions; spare rows that would avoid the reallocation; a
  * dual block beside a lookahead pass. */
 int dlp_session_add_rows(dlp_session* s, int64_t r, const double* G, const double* h, int64_t n,
+                         double* kernel_ms);
+/* Add k variables (columns) to a live session and put it into a primal phase: a
+ * priced-out column, a new advertiser or bid, a new activity, without a new dlp_problem, a new upload
+ * of [A | P] and a cold solve.  P is m x k row-major (column t = the constraint column of new variable
+ * t), d has k entries (its costs); host pointers; any finite value, negative entries and costs
+ * included.  m must be the session's live row count (rows from dlp_session_add_rows included).  The LP
+ * becomes  max [c d]^T [x; w]  s.t.  [A | P] [x; w] <= b.  n becomes n + k; the new variables are
+ * n .. n+k-1 (nonbasic at 0, so the basis stays primal feasible); slack i is renamed from n + i to
+ * n + k + i (dlp_batch_add_cols's renaming: it preserves the order of the old variables, so every tie
+ * rule by variable index decides among them as before).  m, the RHS, the objective value and every old
+ * entry keep their bits.  k == 0 returns DLP_OK and touches nothing (P, d may be NULL).
+ * *kernel_ms (may be NULL): device time of the two kernels of the call together (the widening copy and
+ * the column fold, dlp_addcols.hip).
+ *
+ * Afterwards: status DLP_RUNNING, a primal phase (as after dlp_session_set_objective), the Bland state
+ * reset from the pricing option, no entering column chosen, an empty block, the pricing partials
+ * rebuilt, on K > 1 the RHS cache regathered.  dlp_session_run then does primal pivots on the path
+ * the session is on and ends DLP_OK / DLP_UNBOUNDED / DLP_PIVOT_LIMIT / DLP_RUNNING; the pivot budget
+ * counts from this call.  Pivot-log entries written before the call keep the variable numbers of
+ * their time (a slack logged as n + i then is n + k + i now); entries written afterwards use the new
+ * numbers.
+ *
+ * The column rule is dlp_batch_add_cols's (below), on the session's layouts.  For new
+ * variable t with column p and every stored row r = 0 .. m (the objective row included):
+ *     acc = +0.0;  for l = 0 .. m-1 ascending: acc = acc + (Tfull[r][n+l] * p_l),
+ *   the product rounded, then the sum (no fma).  Constraint rows store acc, the objective row
+ *   acc - d_t (one more rounded subtraction).  One ascending chain per entry; the k columns do not see
+ *   each other; no atomics, no tree, nothing that depends on grid, K, layout or tuning.  A +-0
+ *   coefficient or a +-0 p_l changes no bit of acc (it starts at +0.0 and is never -0.0), so such
+ *   terms may be skipped and no select is needed (unlike the row rule).
+ *   Full layout: Tfull[r][n+l] is the stored entry of column n + l (a basic slack's column is its
+ *     row's unit vector, objective entry +0.0).
+ *   Condensed layout: Tfull[r][n+l] is the entry of slack l's slot when it is nonbasic; 1.0 in the row
+ *     where it is basic; +0.0 otherwise, the objective row included (dlp_session_set_rhs_in_place's
+ *     RHS rule).
+ * Layouts afterwards.  Full: columns [0, n) stay, the new variables are columns [n, n + k), the slack
+ *   block moves from [n, N) to [n + k, N + k), the RHS from N to N + k; the stride follows creation's
+ *   rule for the session's ld_align at the new width.  Condensed: slots [0, n) stay, the new variables
+ *   take slots n .. n+k-1 (nonbasic: var_of[n+t] = n + t, slot_of[n+t] = n + t), the RHS slot moves
+ *   from n to n + k, the stride becomes round16(n + k + 1) (by ld_align); every index >= n in var_of,
+ *   slot_of and basis is raised by k; no restart is pending (every block has been applied).
+ *
+ * Sessions: single-GPU sessions of dense, random and ad-allocation problems on the eager path and on
+ * every deferred path (defer 2..64, full or condensed), in every state but the three of check 3:
+ * optimal, unbounded, or stopped by a budget inside a primal phase (no dual-feasibility check
+ * applies).  A session with lookahead on is accepted: it is drained and turned off, as by
+ * dlp_session_add_rows; dlp_session_set_defer(s, K, condensed, 1) turns it on again.  A block the
+ * step API left open is applied first.
+ *
+ * What follows the new shape: everything sized by n, N, the width or a stride is rebuilt by
+ * creation's rules (the tableau, basis, slot maps, block arrays, selection plans, the pass band, the
+ * cost buffer of dlp_session_set_objective; captured graph windows are dropped).  What stays: the
+ * size class decided at creation, K, the pass form, the caller's band rows, tolerances, pricing, the
+ * pivot log, its capacity and the life-time pivot count.  The dlp_problem handle is not touched, so
+ * the session no longer has its problem's n: dlp_session_set_objective takes n + k costs,
+ * dlp_session_add_rows G with n + k columns, dlp_session_result returns x with n + k entries, and
+ * dlp_session_info, _storage, _tableau, _read_rows, _set_rhs, _set_rhs_in_place, _set_defer and a
+ * second dlp_session_add_cols work as on any session of that shape.  The old and the new tableau
+ * coexist during the call.
+ *
+ * Errors, each leaving the session bit for bit as it was (everything is validated, and every new
+ * buffer allocated, before anything is changed), checked in this order:
+ *   1. DLP_ERR_ARG: s NULL; k < 0; k > 0 with P or d NULL; m differs from the session's m;
+ *      n + k + m + 1 beyond the int32 range of creation (checked before P is read); a P or d entry
+ *      that is not finite (dlp_last_error names it);
+ *   2. DLP_ERR_UNSUPPORTED (text in dlp_last_error): a general or MPS problem; a session created
+ *      with nranks > 1 or an RCCL id; a session on the one-launch small-LP path (create it with
+ *      small_lp = -1: its LDS plan is tied to the shape);
+ *   3. DLP_ERR_STATE: a failed session; a caller-driven step in progress; a dual phase that is
+ *      pending or ended DLP_INFEASIBLE (the RHS has negative entries, which the primal rule must not
+ *      pivot on: finish it with dlp_session_run or call dlp_session_set_rhs);
+ *   4. DLP_ERR_OOM: the widened buffers do not fit beside the old ones.  The shape, every buffer, the
+ *      status, the basis and the tableau are as before, with one difference: a lookahead that was on
+ *      has been drained and turned off (that happens before the allocation;
+ *      dlp_session_get_lookahead reports 0, dlp_session_set_defer turns it on again).
+ * A HIP error during the widening itself (DLP_ERR_HIP) puts the old shape and buffers back as well.
+ * Any k that passes check 1 is handled: the column fold takes one launch per 262,140 columns.
+ * Not covered: removing columns, changing entries of existing columns; device-pointer P / d;
+ * small-LP, multi-rank and general-LP sessions; spare slots that would avoid the reallocation;
+ * keeping the lookahead across the call. */
+int dlp_session_add_cols(dlp_session* s, int64_t k, const double* P, const double* d, int64_t m,
                          double* kernel_ms);
 int dlp_session_buffer(dlp_session* s, int which, void** dev_ptr, size_t* bytes);
 /* Synchronous host copies of an exchange buffer (for host-side communicators). */
@@ -985,8 +1068,8 @@ int dlp_batch_add_rows(dlp_batch* batch, int64_t r, const double* G, int64_t str
  *   dlp_batch_rhs_kernel follow the new shape: a batch with m = 64 keeps the register kernel for
  *   its later resolve calls while n + k <= 192 and leaves it beyond.  This call itself always
  *   runs the LDS kernel.
- * Not covered: removing columns, changing entries of existing columns, general LPs, a single
- * session (a dlp_session_add_cols is not built). */
+ * Not covered: removing columns, changing entries of existing columns, general LPs.  (A single
+ * session: dlp_session_add_cols.) */
 int dlp_batch_add_cols(dlp_batch* batch, int64_t k, const double* P, int64_t strideP, const double* d,
                        int64_t strided, int cols_are_device, int64_t max_pivots, const dlp_batch_out* out);
 /* LP k's resident tableau in the full layout of dlp_session_tableau ((m+1) x dlp_tableau_ld(m,n),
